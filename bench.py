@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- training interactions/sec of the fused BPR embedding step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one minibatch of the hot path (SURVEY.md 8(d), config C2 of BASELINE.json):
@@ -111,14 +111,47 @@ def parse():
     ap.add_argument('--no-configs', action='store_true',
                     help='N=1, C2: skip the compact legs of the other BASELINE.json configurations (the `configs` object of the line)')
     ap.add_argument('--cpu-seconds', type=float, default=30.0)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one handed its caller as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     custom = args.users is not None or args.items is not None
     if args.workload is None:
         args.workload = 'c5' if (args.gpus > 1 and not custom) else 'c2'
+    if args.dump_outputs and (args.gpus > 1 or args.workload not in ('c2', 'c5')):
+        ap.error('--dump-outputs: the training step of --workload c2 / c5 at --gpus 1 only')
     shape = {'c5': (12_500_000, 125_000_000)}.get(args.workload, (10_000_000, 1_000_000))
     args.users = args.users if args.users is not None else shape[0]
     args.items = args.items if args.items is not None else shape[1]
     return args
+
+
+DUMP_BYTES = 64 << 20
+DUMP_MAX_ROWS = 1 << 15
+
+
+def dump_outputs(out_dir, tables, s1, s2, users, items, mb_loss, W, K, B):
+    """--dump-outputs: what the timed path hands its caller after its last step, as float32 / float64 .npy files of at most
+    DUMP_BYTES in all.  The tables are GBs, so the rows are a fixed sample: the users and positive items at DUMP_MAX_ROWS
+    positions of the last timed minibatch (np.random.RandomState(0)), i.e. rows that step updated, with their biases and
+    optimizer state.  minibatch_losses: the K losses of the last timed call."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_state = 1 + (s2 is not None)
+    row_bytes = 2 * (1 + n_state) * (tables[0].shape[1] + 1) * 4 + 2 * 8  # user + item: rows, biases, their state; two ids
+    n = min(B, DUMP_MAX_ROWS, (DUMP_BYTES - 4 * K) // row_bytes)
+    pos = np.sort(np.random.RandomState(0).choice(B, n, replace=False))
+    pos = torch.from_numpy(pos).to(users.device) + (W + K - 1) * B
+    uid, iid = users[pos], items[pos]
+    out = {'minibatch_losses': mb_loss[W:W + K], 'sample_user_ids': uid.double(), 'sample_item_ids': iid.double()}
+    for t, name in enumerate(('user_embeddings', 'item_embeddings', 'user_biases', 'item_biases')):
+        ids = uid if t % 2 == 0 else iid
+        out[name] = tables[t][ids]
+        out[name + '_opt_state1'] = s1[t][ids]
+        if s2 is not None:
+            out[name + '_opt_state2'] = s2[t][ids]
+    for name, x in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), x.cpu().numpy())
 
 
 def main():
@@ -326,6 +359,8 @@ def main():
     be.sync()
     pingpong_merge_ms = (time.perf_counter() - t4) * 1e3 if pingponged else None
     shadow_scope.__exit__(None, None, None)  # (the probes and checks below read the two arrays)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tables, s1, s2, users, items, mb_loss, W, K, B)
     ranks_seen = [{'rank': rank, 'local_rank': local_rank, 'device': be.name}]
     if multi:
         ranks_seen[0]['exchange_rows_timed_call'] = int(xgmi_rows[0])  # lookups of this rank that crossed to another rank, K steps

@@ -124,6 +124,35 @@ def test_row_sharded_bench_loop_on_the_bias_shadow():
     assert final[0] == final[1] and final[0] > 0
 
 
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: float32 / float64 .npy files of at most 64 MB holding the last timed call's K minibatch losses and
+    sampled rows of the tables and optimizer state; the same arguments give the same inputs, so two runs write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ('a', 'b'):
+        d = tmp_path / run
+        rc, out, err = run_bench(['--gpus', '1', '--steps', '3', '--dump-outputs', str(d)])
+        assert rc == 0, err[-3000:]
+        rec = json.loads([l for l in out.splitlines() if l.strip().startswith('{')][-1])
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(d)) if f.endswith('.npy')}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        loss = arrs['minibatch_losses']
+        assert loss.shape == (3,) and loss[-1] == np.float32(rec['final_minibatch_loss']) and (loss > 0).all()
+        assert arrs['user_embeddings'].shape == arrs['item_embeddings'].shape == (256, 16)
+        assert arrs['item_biases_opt_state1'].shape == (256,) and (arrs['item_biases_opt_state1'] > 0).all()  # every sampled row stepped
+        dumps.append(arrs)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
+
+
+def test_dump_outputs_refuses_other_workloads():
+    rc, out, err = run_bench(['--gpus', '1', '--workload', 'c4', '--dump-outputs', 'unused'])
+    assert rc != 0 and '--dump-outputs' in err and not out.strip()
+
+
 def test_world_size_mismatch_fails_loudly():
     rc, out, err = run_bench(['--gpus', '2'], env_extra={'WORLD_SIZE': '1', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert rc != 0 and 'WORLD_SIZE' in err and not out.strip()
