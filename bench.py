@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- training interactions/sec of the fused BPR embedding step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one minibatch of the hot path (SURVEY.md 8(d), config C2 of BASELINE.json):
@@ -10,7 +10,14 @@ synthetic uniform ids over 10M users x 1M items, dim 64, bpr loss, Adagrad(lr=1e
 (gather + dot + loss + backward + optimizer), all inside the timed region, ids resident in
 HBM beforehand.  value = interactions processed by all ranks / max-over-ranks wall time.
 
-Extra objects on the JSON line:
+A plain run does what the headline figure needs and nothing else: set-up, the W warm-up steps, the K-step calls (below), the
+--dump-outputs files, the line.  Everything else the benchmark measures or checks runs under --full only: the kernel timers and
+the `roofline` object, the bandwidth probes, the row-sharded consistency run, the fit() leg, the `configs` legs of the other
+configurations, the CPU baselines, and at N > 1 rank 0's one-GPU denominators.  The --no-* options take single pieces out of a
+--full run; a plain run ignores them.  Both kinds of run make the same training calls in the same order, so `value`,
+`ms_per_step` and the dumped arrays are those of the same work.
+
+Extra objects on the JSON line of a --full run:
   roofline     dominant kernel: algorithmic bytes per launch / mean launch
                duration from hipEvents recorded on the launch stream (slk_profile_*)
   cpu_baseline Spotlight's own CPU PyTorch path (oracle/_ref, staged by oracle/make_ref.sh) timed on the
@@ -44,6 +51,10 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=16)
     ap.add_argument('--warmup', type=int, default=4)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything besides the headline figure: kernel timers + the `roofline` object, bandwidth probes, '
+                         'the row-sharded consistency run, the fit() leg, the `configs` legs, the CPU baselines, N > 1: the one-GPU '
+                         'denominators (minutes; the --no-* options below take single pieces out again).  Default: none of them')
     ap.add_argument('--users', type=int, default=None, help='user rows per GPU (default: the workload\'s)')
     ap.add_argument('--items', type=int, default=None, help='item rows per GPU (default: the workload\'s)')
     ap.add_argument('--dim', type=int, default=64)
@@ -59,7 +70,7 @@ def parse():
                          '100M-user table (12.5M users x 125M items per GPU; at --gpus 8 the full C5; the default at --gpus > 1: '
                          'the row-sharded configuration BASELINE.json names).  Explicit --users / --items override the shape.')
     ap.add_argument('--no-denominators', action='store_true',
-                    help='N > 1: skip rank 0\'s world-1 runs of the same per-GPU shape (fused path, row-sharded path) that give '
+                    help='--full, N > 1: skip rank 0\'s world-1 runs of the same per-GPU shape (fused path, row-sharded path) that give '
                          'the scaling factor its stated denominators')
     ap.add_argument('--seq-len', type=int, default=200)
     ap.add_argument('--pad-frac', type=float, default=0.0,
@@ -76,7 +87,7 @@ def parse():
                     help='user ids drawn with probability ~ 1 / rank^s through a random rank -> id map (0 = uniform, the default and '
                          'the metric\'s distribution): power users, a stress run for the user pass\'s long-run form')
     ap.add_argument('--no-fit', action='store_true',
-                    help='N=1, C2: skip the end-to-end ImplicitFactorizationModel.fit() measurement (the drop-in API around the engine)')
+                    help='--full, N=1, C2: skip the end-to-end ImplicitFactorizationModel.fit() measurement (the drop-in API around the engine)')
     ap.add_argument('--fit-interactions', type=int, default=1 << 25)
     ap.add_argument('--shard-chunk', type=int, default=8,
                     help='row-sharded path: minibatches per chunk (one count exchange + host synchronisation per chunk)')
@@ -87,12 +98,12 @@ def parse():
                     help="hip: the product (libspotlight_hip.so on MI355X, RCCL).  emu: TEST HARNESS ONLY -- the same host code over "
                          "tests/emu's CPU build of the kernels and gloo, so that the N > 1 launch path can be exercised on a box "
                          "without GPUs (tests/test_bench_cli.py); never a measurement")
-    ap.add_argument('--no-probes', action='store_true', help='skip the copy / triad / step-ceiling bandwidth probes')
+    ap.add_argument('--no-probes', action='store_true', help='--full: skip the copy / triad / step-ceiling bandwidth probes')
     ap.add_argument('--no-sharded-check', action='store_true',
-                    help='N=1: skip the consistency run of the row-sharded path (world 1) against the fused path')
+                    help='--full, N=1: skip the consistency run of the row-sharded path (world 1) against the fused path')
     ap.add_argument('--no-overlapped', action='store_true',
-                    help='skip the secondary roofline.overlapped measurement (three more K-step calls with option overlap_prep = 1): what '
-                         'the rocprofv3 / PMC commands use, so that their per-kernel means are those of the timed configuration only')
+                    help='skip the three K-step calls with option overlap_prep = 1 (--full: the secondary roofline.overlapped measurement): '
+                         'what the rocprofv3 / PMC commands use, so that their per-kernel means are those of the timed configuration only')
     ap.add_argument('--no-bias-shadow', action='store_true',
                     help='item tables of 2^24 rows and more: keep the item biases and their Adagrad accumulator in two arrays '
                          '(default: interleaved for the run, as fit() trains such tables -- slk_bias_shadow_begin, opened before '
@@ -107,10 +118,10 @@ def parse():
     ap.add_argument('--bias-shadow-min-items', type=int, default=1 << 24,
                     help='item rows per GPU from which the run trains on the bias shadow (tests force it at small sizes)')
     ap.add_argument('--no-loss-check', action='store_true', help='measurement of debug modes whose results are meaningless')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the cpu_baseline object')
     ap.add_argument('--no-configs', action='store_true',
-                    help='N=1, C2: skip the compact legs of the other BASELINE.json configurations (the `configs` object of the line)')
-    ap.add_argument('--cpu-seconds', type=float, default=30.0)
+                    help='--full, N=1, C2: skip the compact legs of the other BASELINE.json configurations (the `configs` object of the line)')
+    ap.add_argument('--cpu-seconds', type=float, default=30.0, help='--full: time budget of the cpu_baseline object')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one handed its caller as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
@@ -184,7 +195,8 @@ def main():
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     dist = None
     be = Backend(args.backend, local_rank)
-    want_sharded_check = (world == 1 and not args.sharded and not args.no_sharded_check and args.workload in ('c2', 'c5')
+    full = args.full
+    want_sharded_check = (full and world == 1 and not args.sharded and not args.no_sharded_check and args.workload in ('c2', 'c5')
                           and args.loss != 'adaptive_hinge')
     if world > 1 or args.sharded:
         dist = be.init_dist(rank, world, local_rank)
@@ -276,11 +288,11 @@ def main():
             dist.barrier()
             be.sync()
 
-    # The copy / triad probes (own buffers, the tables untouched) go BEFORE the warm-up: a GPU coming out of idle runs its first
+    # --full: the copy / triad probes (own buffers, the tables untouched) go BEFORE the warm-up: a GPU coming out of idle runs its first
     # ~20 ms 4-6 % slower (profiles/r03_t_first_call_after_idle.txt: the figure returns after 0.5 s of idle), and W = 5 warm-up
     # minibatches are 4 ms.  The timed region itself is unchanged: W untimed steps, then exactly K.
     probes = ceiling = shard_check = None
-    want_probes = rank == 0 and world == 1 and trainer is None and not args.no_probes
+    want_probes = full and rank == 0 and world == 1 and trainer is None and not args.no_probes
     if want_probes:
         probes = measured_stream_rates(be, stream)
     if trainer is None:
@@ -296,27 +308,33 @@ def main():
     be.sync()
     elapsed = time.perf_counter() - t0
     barrier()
-    # per-kernel durations: K more steps with hipEvents around every launch (slk_profile_*);
+    # K more steps, then (N = 1) three times the same K with option overlap_prep = 1.  The line's value is the steady state BEHIND
+    # these calls (below) and --dump-outputs records the tables after them, so every run makes them; what --full adds is their
+    # instrumentation.
+    # --full, per-kernel durations: these K steps with hipEvents around every launch (slk_profile_*);
     # outside the timed region because the event records themselves cost ~10 us per launch
     xg, xgb = xgmi_rows[0], list(xgmi_bytes)
-    eng.profile_reset()
-    eng.profile_enable(True)
-    single0 = eng.get_stat('single_minibatches')
+    prof = single_mb = None
+    if full:
+        eng.profile_reset()
+        eng.profile_enable(True)
+        single0 = eng.get_stat('single_minibatches')
     t1 = time.perf_counter()
     run(W + K, K)
     be.sync()
     elapsed_profiled = time.perf_counter() - t1
-    eng.profile_enable(False)
-    prof = eng.profile_read()
-    # minibatches of the instrumented call whose once-only items were updated by the USER pass (option "item_single_min_items":
-    # catalogues far larger than a minibatch): the pass then carries those items' algorithmic bytes too
-    single_mb = eng.get_stat('single_minibatches') - single0
+    if full:
+        eng.profile_enable(False)
+        prof = eng.profile_read()
+        # minibatches of the instrumented call whose once-only items were updated by the USER pass (option "item_single_min_items":
+        # catalogues far larger than a minibatch): the pass then carries those items' algorithmic bytes too
+        single_mb = eng.get_stat('single_minibatches') - single0
     xgmi_rows[0] = xg
     xgmi_bytes[:] = xgb
     # The timed region above runs a bare ctx's default: negatives, sorts and passes in order on one stream.  fit() switches
     # the ctx to "overlap_prep" (the next chunk's negatives + sorts on a second stream beside the passes); the same K
-    # minibatches are run that way three more times -- untimed warm-up, un-instrumented, with the kernel timers -- and go
-    # into the line as roofline.overlapped: the steady state a training run of many calls sees.
+    # minibatches are run that way three more times -- untimed warm-up, un-instrumented, with the kernel timers (--full) -- and go
+    # into a --full line as roofline.overlapped: the steady state a training run of many calls sees.
     prof_ov = elapsed_ov = elapsed_ov_prof = None
     if trainer is None and world == 1 and not args.no_overlapped and not any(kv.startswith('overlap_prep=') for kv in args.set):
         eng.set_option('overlap_prep', 1)
@@ -328,14 +346,16 @@ def main():
             run(W + K, K)
             be.sync()
             elapsed_ov = time.perf_counter() - t2
-            eng.profile_reset()
-            eng.profile_enable(True)
+            if full:
+                eng.profile_reset()
+                eng.profile_enable(True)
             t2 = time.perf_counter()
             run(W + K, K)
             be.sync()
             elapsed_ov_prof = time.perf_counter() - t2
-            eng.profile_enable(False)
-            prof_ov = eng.profile_read()
+            if full:
+                eng.profile_enable(False)
+                prof_ov = eng.profile_read()
         finally:
             eng.set_option('overlap_prep', 0)
     # The line's value: the same K minibatches once more, in line on one stream as in the first timed call, now that the process
@@ -380,7 +400,7 @@ def main():
         ranks_seen = seen
         assert dist.get_world_size() == world == args.gpus or args.sharded, (dist.get_world_size(), world, args.gpus)
     denominators = None
-    if world > 1 and not args.no_denominators:
+    if full and world > 1 and not args.no_denominators:
         # What the N-GPU value is a multiple OF (--gpus 1 runs the fused path on C2, --gpus N the row-sharded
         # path): rank 0 runs the SAME per-GPU shape alone, through the fused path and through the row-sharded path at world 1.
         g1 = dist.new_group([0])  # every rank makes the call
@@ -439,7 +459,7 @@ def main():
             shard_check = {'error': repr(e)[:300]}
 
     fit_rec = None
-    if rank == 0 and world == 1 and trainer is None and be.kind == 'hip' and args.workload == 'c2' and not args.no_fit:
+    if full and rank == 0 and world == 1 and trainer is None and be.kind == 'hip' and args.workload == 'c2' and not args.no_fit:
         try:
             del users, items
             fit_rec = fit_end_to_end(be, args)
@@ -448,7 +468,7 @@ def main():
 
     legs = None
     default_shape = (args.users, args.items, args.dim, args.batch, args.loss, args.opt) == (10_000_000, 1_000_000, 64, 1 << 20, 'bpr', 'adagrad')
-    if (rank == 0 and world == 1 and trainer is None and be.kind == 'hip' and args.workload == 'c2' and default_shape
+    if (full and rank == 0 and world == 1 and trainer is None and be.kind == 'hip' and args.workload == 'c2' and default_shape
             and not args.no_configs and not args.item_zipf and not args.user_zipf):
         from benchlib.legs import run_config_legs
         try:
@@ -461,26 +481,28 @@ def main():
     losses = losses[:W + K]
 
     if rank == 0:
-        value, roof = build_roofline(args, world=world, K=K, B=B, D=D, elapsed=elapsed, prof=prof, prof_ov=prof_ov,
-                                     elapsed_ov=elapsed_ov, elapsed_ov_prof=elapsed_ov_prof, probes=probes, ceiling=ceiling,
-                                     trainer=trainer, xgmi_rows=xgmi_rows, denominators=denominators, xgmi_bytes=xgmi_bytes)
-        if pingpong_merge_ms is not None:
-            roof['pingpong_merge_ms'] = pingpong_merge_ms
-        if single_mb == K and trainer is None:
-            # the single-occurrence fast path ran in every minibatch: the two kernels' shares of the step's algorithmic bytes are no
-            # longer 1576 / 1560 -- the user pass updates the items that occur once (nearly all on such a catalogue), the item pass
-            # only walks the sorted list.  The dominant kernel is priced on the WHOLE step's algorithmic bytes (an upper bound of its
-            # share: the few multi-occurrence items are still the item pass's)
-            ku = roof['kernels']['user_pass']
-            step_b = roof['step_alg_bytes_per_interaction'] * B
-            ku['alg_bytes_per_launch'] = step_b
-            ku['achieved_GBs'] = step_b / (ku['avg_ms'] * 1e-3) / 1e9
-            roof['kernels']['item_pass']['alg_bytes_per_launch'] = 0
-            roof['kernels']['item_pass']['achieved_GBs'] = 0.0
-            roof.update({'kernel': 'k_user_pass', 'achieved': ku['achieved_GBs'], 'frac': ku['achieved_GBs'] / roof['peak'], 'traffic': None,
-                         'single_occurrence_fast_path': 'every minibatch: items that occur once in their minibatch are updated by the user '
-                                                        'pass (include/spotlight_hip.h, option item_single_min_items); the user pass is priced '
-                                                        'on the whole step\'s algorithmic bytes, the item pass on none'})
+        value, roof = world * K * B / elapsed, None
+        if full:
+            value, roof = build_roofline(args, world=world, K=K, B=B, D=D, elapsed=elapsed, prof=prof, prof_ov=prof_ov,
+                                         elapsed_ov=elapsed_ov, elapsed_ov_prof=elapsed_ov_prof, probes=probes, ceiling=ceiling,
+                                         trainer=trainer, xgmi_rows=xgmi_rows, denominators=denominators, xgmi_bytes=xgmi_bytes)
+            if pingpong_merge_ms is not None:
+                roof['pingpong_merge_ms'] = pingpong_merge_ms
+            if single_mb == K and trainer is None:
+                # the single-occurrence fast path ran in every minibatch: the two kernels' shares of the step's algorithmic bytes are no
+                # longer 1576 / 1560 -- the user pass updates the items that occur once (nearly all on such a catalogue), the item pass
+                # only walks the sorted list.  The dominant kernel is priced on the WHOLE step's algorithmic bytes (an upper bound of its
+                # share: the few multi-occurrence items are still the item pass's)
+                ku = roof['kernels']['user_pass']
+                step_b = roof['step_alg_bytes_per_interaction'] * B
+                ku['alg_bytes_per_launch'] = step_b
+                ku['achieved_GBs'] = step_b / (ku['avg_ms'] * 1e-3) / 1e9
+                roof['kernels']['item_pass']['alg_bytes_per_launch'] = 0
+                roof['kernels']['item_pass']['achieved_GBs'] = 0.0
+                roof.update({'kernel': 'k_user_pass', 'achieved': ku['achieved_GBs'], 'frac': ku['achieved_GBs'] / roof['peak'], 'traffic': None,
+                             'single_occurrence_fast_path': 'every minibatch: items that occur once in their minibatch are updated by the user '
+                                                            'pass (include/spotlight_hip.h, option item_single_min_items); the user pass is priced '
+                                                            'on the whole step\'s algorithmic bytes, the item pass on none'})
         out = {'metric': 'training interactions/sec, BPR dim=64', 'value': value, 'unit': 'interactions/s',
                'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': elapsed / K * 1e3,
                'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
@@ -508,21 +530,24 @@ def main():
                           'row-sharded x%d: users and items sharded cyclically; RCCL all-to-all of ids per chunk of '
                           'minibatches, of rows and gradient rows per user-slice of a minibatch (async, overlapping '
                           'the other slices\' compute); no replicas' % world},
-               'roofline': roof,
-               'ms_per_step_with_kernel_timers': elapsed_profiled / K * 1e3,
+               'full': full,
                'timed_region': 'exactly K minibatches between barrier + device sync, negatives, sorts and passes in order on one '
-                               'stream; the LAST K-step call of the run (after the W warm-up steps, the first K-step call, the '
-                               'instrumented one and the roofline.overlapped leg): the steady state of a training run',
+                               'stream; the LAST K-step call of the run (after the W warm-up steps, the first K-step call, one more '
+                               'in line and at N = 1 three with overlap_prep = 1 -- under --full the instrumented one and the '
+                               'roofline.overlapped leg): the steady state of a training run',
                'first_call': {'ms_per_step': elapsed_first / K * 1e3, 'interactions_per_s': world * K * B / elapsed_first,
                               'note': 'the first K-step call of the process, straight after the W warm-up steps (what rounds 1-3 '
                                       'printed as value): the GPU is still leaving its idle power state, '
                                       'profiles/r04_o_first_call_of_a_process.txt'},
                'final_minibatch_loss': float(losses[-1])}
+        if full:
+            out['roofline'] = roof
+            out['ms_per_step_with_kernel_timers'] = elapsed_profiled / K * 1e3
         if shard_check is not None:
             out['sharded_world1_consistency'] = shard_check
         if fit_rec is not None:
             out['fit_end_to_end'] = fit_rec
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # the reference itself on this box's host cores; the scalar C port (1 thread) as a secondary field
             ref = reference_cpu_baseline(args, args.cpu_seconds * 2.0 / 3.0)  # the timed fits' share; its set-up comes on top
             port = cpu_baseline(args, 6.0 if ref and 'value' in ref else args.cpu_seconds)

@@ -12,7 +12,8 @@ import time
 
 from benchlib.common import ROOT
 
-_QUIET = ['--no-cpu-baseline', '--no-fit', '--no-probes', '--no-sharded-check', '--no-overlapped', '--no-configs']
+# the headline workload's legs: --full for the kernel timers (the `roofline` object _compact reads), less every other extra
+_QUIET = ['--full', '--no-cpu-baseline', '--no-fit', '--no-probes', '--no-sharded-check', '--no-overlapped', '--no-configs']
 # name -> (arguments, how to read the leg's own JSON line)
 # Step counts (round 6): every training leg runs SEVERAL prep chunks per call (C2-sized minibatches: 20 steps = 3 chunks; C4: 40 steps
 # = 4 chunks of 10 minibatches; C3: 64 steps = 2 chunks of 32), as any epoch of a training run does -- with one chunk per call (rounds

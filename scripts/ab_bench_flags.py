@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Same-box A/B of bench.py flag sets: scripts/ab_bench_flags.py <rounds> <common flags> -- <flags A> -- <flags B> ...
-Prints ms/step, the dominant kernel's roofline fraction and the per-kernel ms/step of every run (alternating A, B, A, B ...)."""
+Prints ms/step, the dominant kernel's roofline fraction and the per-kernel ms/step of every run (alternating A, B, A, B ...).
+Every run is a --full one (the kernel timers); the --no-* flags among the common ones take out what an A/B does not need."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def main():
     common, variants = groups[0], groups[1:]
     for r in range(rounds):
         for v in variants:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + common + v, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+            p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full'] + common + v, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                universal_newlines=True)
             line = [l for l in p.stdout.splitlines() if l.startswith('{')]
             if not line:

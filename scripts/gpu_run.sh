@@ -5,9 +5,9 @@
 #   tests            pytest -m gpu (whole suite)          tests:<expr>   pytest -m gpu -k <expr>
 #   parity           tests/test_gpu_bench_parity.py       smoke          __graft_entry__.smoke()
 #   sort             tests/test_gpu_sort.py + scripts/bench_sort.py
-#   bench[:<args>]   bench.py <args> (':' separates arguments: bench:--workload:c4:--steps:8)
-#   prof[:<args>]    rocprofv3 --kernel-trace --stats of bench.py <args> -> kernel_stats*.md
-#   pmc[:<args>]     rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py <args>
+#   bench[:<args>]   bench.py <args> (':' separates arguments: bench:--workload:c4:--steps:8; bench:--full for the whole line)
+#   prof[:<args>]    rocprofv3 --kernel-trace --stats of bench.py --full <args> -> kernel_stats*.md
+#   pmc[:<args>]     rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py --full <args>
 #   sweep:<name>:<cfg>[:<cfg>...]   scripts/sweep_engine.py --configs <cfg> ... (cfg = 'opt=v,opt=v'); extra sweep_engine
 #                    arguments through SWEEP_ARGS
 #   py:<script>[:<args>]   python scripts/<script> <args>
@@ -40,13 +40,13 @@ for st in "$@"; do
     bench)
       timeout 900 python bench.py "${args[@]}" > $OUT/bench_$sfx.json 2> $OUT/bench_$sfx.err; echo "bench ${args[*]:-} exit $?"; cut -c1-1500 $OUT/bench_$sfx.json; tail -3 $OUT/bench_$sfx.err ;;
     prof)
-      (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_$sfx -o bench -- python $ROOT/bench.py "${args[@]}" --no-cpu-baseline > $OUT/prof_bench_$sfx.json 2> $OUT/prof_$sfx.err)
+      (cd $TMPDIR && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_$sfx -o bench -- python $ROOT/bench.py --full "${args[@]}" --no-cpu-baseline > $OUT/prof_bench_$sfx.json 2> $OUT/prof_$sfx.err)
       echo "prof exit $?"
       db=$(find $OUT/prof_$sfx -name "*.db" | head -1)
-      [ -n "$db" ] && python $ROOT/scripts/summarize_prof.py "$db" $OUT/kernel_stats_$sfx.md "rocprofv3 --kernel-trace --stats -- python bench.py ${args[*]:-} --no-cpu-baseline ($TAG)" $OUT/prof_bench_$sfx.json && rm -rf $OUT/prof_$sfx && head -40 $OUT/kernel_stats_$sfx.md ;;
+      [ -n "$db" ] && python $ROOT/scripts/summarize_prof.py "$db" $OUT/kernel_stats_$sfx.md "rocprofv3 --kernel-trace --stats -- python bench.py --full ${args[*]:-} --no-cpu-baseline ($TAG)" $OUT/prof_bench_$sfx.json && rm -rf $OUT/prof_$sfx && head -40 $OUT/kernel_stats_$sfx.md ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
-        (cd /tmp && timeout 900 rocprofv3 --pmc $c -d $OUT/pmc_${c}_$sfx -o bench -- python $ROOT/bench.py "${args[@]}" --no-cpu-baseline > $OUT/pmc_${c}_$sfx.json 2> $OUT/pmc_${c}_$sfx.err)
+        (cd $TMPDIR && timeout 900 rocprofv3 --pmc $c -d $OUT/pmc_${c}_$sfx -o bench -- python $ROOT/bench.py --full "${args[@]}" --no-cpu-baseline > $OUT/pmc_${c}_$sfx.json 2> $OUT/pmc_${c}_$sfx.err)
         echo "pmc $c exit $?"
       done
       python $ROOT/scripts/summarize_pmc.py $OUT > $OUT/pmc_$sfx.md 2>&1; head -30 $OUT/pmc_$sfx.md ;;

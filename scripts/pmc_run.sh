@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 run() {  # name, counters...
   local name=$1; shift
-  timeout 600 rocprofv3 --pmc "$@" -d $OUT/$name -o pmc -- python $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-fit "${BARGS[@]}" > $OUT/$name.json 2> $OUT/$name.err
+  timeout 600 rocprofv3 --pmc "$@" -d $OUT/$name -o pmc -- python $ROOT/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-fit "${BARGS[@]}" > $OUT/$name.json 2> $OUT/$name.err
   echo "pmc $name exit $?"
 }
 BARGS=("$@")
@@ -32,6 +32,6 @@ if [ -n "${PMC_EA:-}" ]; then
   # (a TA_* group -- TA_ADDR_STALLED_BY_TC_CYCLES_sum, TA_DATA_STALLED_BY_TC_CYCLES_sum, TA_TA_BUSY_sum -- never returned on
   # this pool: rocprofv3 sat until the time-out, twice 600 s of box time in round 4.  Not collected.)
 fi
-python $ROOT/scripts/summarize_pmc.py $OUT $OUT/pmc_summary "rocprofv3 --pmc passes over python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-fit ${BARGS[*]} ($TAG)" > /dev/null
+python $ROOT/scripts/summarize_pmc.py $OUT $OUT/pmc_summary "rocprofv3 --pmc passes over python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-fit ${BARGS[*]} ($TAG)" > /dev/null
 for g in fetch write sq tcc utcl1 tcpreq ea_rd ea_wr; do rm -rf $OUT/$g; done
 ls $OUT; cat $OUT/pmc_summary.md | head -60

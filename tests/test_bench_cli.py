@@ -26,8 +26,38 @@ def run_bench(extra, env_extra=None, timeout=900):
     return p.returncode, p.stdout.decode(), p.stderr.decode()
 
 
+EXTRAS = ('roofline', 'ms_per_step_with_kernel_timers', 'sharded_world1_consistency', 'fit_end_to_end', 'cpu_baseline', 'configs')
+
+
+def test_plain_run_prints_the_headline_line_and_nothing_that_takes_a_run_of_its_own():
+    """Without --full: one JSON line with the contract fields, none of the objects that --full adds -- and the --no-* options,
+    which take pieces out of a --full run, change nothing about it."""
+    for extra in ([], ['--no-probes', '--no-sharded-check', '--no-fit', '--no-configs', '--no-denominators']):
+        rc, out, err = run_bench(['--gpus', '1'] + extra)
+        assert rc == 0, err[-3000:]
+        lines = [l for l in out.splitlines() if l.strip()]
+        assert len(lines) == 1, out
+        rec = json.loads(lines[0])
+        for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                    'vs_baseline', 'dtype', 'data', 'config', 'first_call', 'final_minibatch_loss'):
+            assert key in rec, key
+        assert rec['full'] is False and not [k for k in EXTRAS if k in rec], sorted(rec)
+        assert rec['n_gpus'] == 1 and rec['steps'] == 2 and rec['warmup'] == 1 and rec['higher_is_better'] is True
+        assert rec['ms_per_step'] > 0 and abs(rec['value'] * rec['ms_per_step'] * 1e-3 - 256) < 1e-6 * 256  # = batch / step time
+        assert rec['ranks']['world_size_observed'] == 1 and rec['final_minibatch_loss'] > 0
+
+
+def test_plain_n_gpu_run_has_no_denominators():
+    rc, out, err = run_bench(['--gpus', '2'])
+    assert rc == 0, err[-3000:]
+    rec = json.loads([l for l in out.splitlines() if l.strip().startswith('{')][-1])
+    assert rec['n_gpus'] == 2 and rec['ranks']['world_size_observed'] == 2 and rec['full'] is False
+    assert not [k for k in EXTRAS if k in rec], sorted(rec)
+    assert all(d['exchange_rows_timed_call'] > 0 for d in rec['ranks']['devices']) and rec['final_minibatch_loss'] > 0
+
+
 def test_single_rank_line_has_the_contract_fields():
-    rc, out, err = run_bench(['--gpus', '1'])
+    rc, out, err = run_bench(['--gpus', '1', '--full'])
     assert rc == 0, err[-3000:]
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1, out  # exactly ONE JSON line on stdout
@@ -40,6 +70,7 @@ def test_single_rank_line_has_the_contract_fields():
     for key in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'measured', 'ceiling'):
         assert key in roof, key
     assert roof['measured']['copy_GBs'] > 0 and roof['ceiling']['ms_per_step'] > 0
+    assert rec['full'] is True and rec['ms_per_step_with_kernel_timers'] > 0
     chk = rec['sharded_world1_consistency']
     assert chk.get('consistent') is True, chk
     assert rec['ranks']['world_size_observed'] == 1
@@ -47,8 +78,9 @@ def test_single_rank_line_has_the_contract_fields():
 
 @pytest.mark.parametrize('n', [2, 4])
 def test_gpus_n_spawns_n_ranks_itself(n):
-    """`python bench.py --gpus N` with no torchrun environment launches the N ranks itself."""
-    rc, out, err = run_bench(['--gpus', str(n)])
+    """`python bench.py --gpus N` with no torchrun environment launches the N ranks itself (--full: the line's xGMI accounting
+    and rank 0's one-GPU denominators)."""
+    rc, out, err = run_bench(['--gpus', str(n), '--full'])
     assert rc == 0, err[-3000:]
     lines = [l for l in out.splitlines() if l.strip().startswith('{')]
     assert len(lines) == 1, out
@@ -73,7 +105,7 @@ def test_default_n_gpu_configuration_c5_at_reduced_rows(n):
     at reduced rows: the line names the workload, the process group saw N ranks, every rank reports the lookups it sent to other
     ranks (about (N - 1) / N of its 2 B K), and rank 0's own world-1 runs of the same per-GPU shape -- fused path and
     row-sharded path -- agree on every minibatch's loss."""
-    rc, out, err = run_bench(['--gpus', str(n), '--workload', 'c5'])
+    rc, out, err = run_bench(['--gpus', str(n), '--workload', 'c5', '--full'])
     assert rc == 0, err[-3000:]
     rec = json.loads([l for l in out.splitlines() if l.strip().startswith('{')][-1])
     assert rec['config']['workload'].startswith('C5') and 'row-sharded x%d' % n in rec['config']['parallelism']
@@ -112,7 +144,7 @@ def test_row_sharded_bench_loop_on_the_bias_shadow():
     reduced rows): the same per-minibatch loss as the plain layout -- same seeds, same draws --, and the line says which layout ran."""
     final = []
     for extra in (['--bias-shadow-min-items', '1'], ['--no-bias-shadow']):
-        rc, out, err = run_bench(['--gpus', '2', '--workload', 'c5'] + extra)
+        rc, out, err = run_bench(['--gpus', '2', '--workload', 'c5', '--full'] + extra)
         assert rc == 0, err[-3000:]
         rec = json.loads([l for l in out.splitlines() if l.strip().startswith('{')][-1])
         assert rec['config']['item_bias_layout'].startswith('two arrays') == (extra[0] == '--no-bias-shadow')
@@ -144,6 +176,23 @@ def test_dump_outputs_of_the_last_timed_step(tmp_path):
         assert arrs['item_biases_opt_state1'].shape == (256,) and (arrs['item_biases_opt_state1'] > 0).all()  # every sampled row stepped
         dumps.append(arrs)
     assert sorted(dumps[0]) == sorted(dumps[1])
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
+
+
+def test_full_run_trains_what_a_plain_run_trains(tmp_path):
+    """--full adds measurements around the training calls, never a training step: same losses, same dumped arrays, bit for bit."""
+    import numpy as np
+    dumps, final = [], []
+    for name, extra in (('plain', []), ('full', ['--full'])):
+        d = tmp_path / name
+        rc, out, err = run_bench(['--gpus', '1', '--steps', '3', '--dump-outputs', str(d)] + extra)
+        assert rc == 0, err[-3000:]
+        rec = json.loads([l for l in out.splitlines() if l.strip().startswith('{')][-1])
+        assert rec['full'] is (name == 'full') and ('roofline' in rec) == (name == 'full')
+        final.append(rec['final_minibatch_loss'])
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(d)) if f.endswith('.npy')})
+    assert final[0] == final[1] and sorted(dumps[0]) == sorted(dumps[1]) and 'minibatch_losses' in dumps[0]
     for name in dumps[0]:
         np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
 
