@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SLK_ABI_VERSION 12
+#define SLK_ABI_VERSION 13
 
 #define SLK_OK 0
 #define SLK_EIO (-5)
@@ -561,6 +561,36 @@ int slk_shard_adaptive_select(slk_ctx *ctx, int64_t global_batch, int32_t n_neg,
                               float *d_loss_out, int32_t report_loss, void *stream);
 int slk_shard_user_pass_adaptive(slk_ctx *ctx, const slk_tables *local, const slk_optim *optim, int32_t unit,
                                  const float *d_gk, const float *d_rows_in, float *d_grad_out, void *stream);
+
+/* Evaluation of a row-sharded model, shard by shard (ABI 13).  `local` is this rank's shard, as above, and only its ITEM side
+ * is read (d_param[1], d_param[3], num_items, dim; the user-side pointers may be NULL): a group's user row usually lives on
+ * another rank, so the groups' representations come as dense device arrays d_rep[n_groups][dim] / d_rbias[n_groups] (the
+ * user's embedding row and bias; the host assembles them from their owners, n_groups * (dim + 1) floats on the wire).
+ * Every score is the one-device chain, (dot + rbias) + bi, on whichever unit forms it, and the counts are integers, so the
+ * ranks' results combine EXACTLY into what slk_bilinear_rank / slk_bilinear_scores return on the whole table:
+ *   slk_shard_target_scores  d_st_out[r] = the score of row r's target where this rank owns it (d_row_target_local[r]: its
+ *                            LOCAL item row), -FLT_MAX where the target is on its group's local exclusion list; -INFINITY
+ *                            where d_row_target_local[r] is -1: another rank's (any value outside [0, num_items) is treated so)
+ *        [all-reduce(MAX) of d_st_out over the ranks: exactly one rank owns a target, and the same rank holds its exclusion entry]
+ *   slk_shard_rank_counts    d_gt_out[r] / d_eq_out[r] = #{local items scoring > / == d_st[r]}, d_st the GLOBAL target scores,
+ *                            the group's local exclusion list counted at -FLT_MAX (one counting sweep of the local rows per
+ *                            64 rows on the matrix cores; no score matrix)
+ *        [all-reduce(SUM) of both arrays; rank = gt + (eq + 1) / 2 in double: scipy's 'average']
+ *   slk_shard_scores         d_out[r * num_items + j] = score of LOCAL item row j for representation r: this rank's columns
+ *                            of the rows slk_bilinear_scores returns (global item j * world + rank)
+ * d_row_group[r]: row r's group; d_exc_off[n_groups + 1] / d_exc_items_local: per group the LOCAL rows of its excluded items
+ * that this rank owns (CSR, rebuilt per rank; every item at most once per group; d_exc_off NULL: none).  All ranks make the
+ * same calls; a rank that owns no item row makes no call and contributes -INFINITY / zeros to the collectives.  Plain item
+ * tables only (a bloom table is refused), and not inside a bias-shadow scope of these item biases.  Nothing is retained: every
+ * pointer may be freed or reused once the stream has run the call; scratch is the ctx's (shared with the fused ranking). */
+int slk_shard_target_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_groups,
+                            const int64_t *d_row_group, const int64_t *d_row_target_local, int64_t n_rows,
+                            const int64_t *d_exc_off, const int64_t *d_exc_items_local, float *d_st_out, void *stream);
+int slk_shard_rank_counts(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_groups,
+                          const int64_t *d_row_group, const float *d_st, int64_t n_rows, const int64_t *d_exc_off,
+                          const int64_t *d_exc_items_local, int64_t *d_gt_out, int64_t *d_eq_out, void *stream);
+int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
+                     float *d_out, void *stream);
 
 /* Measurement support (the reference has none; examples/bloom_embeddings/performance.py
  * times fit() with time.time()): when enabled, every launch of the engine's kernels is

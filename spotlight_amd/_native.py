@@ -13,7 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libspotlight_hip.so')
 
-SLK_ABI_VERSION = 12
+SLK_ABI_VERSION = 13
 SLK_OK, SLK_EIO, SLK_ENOMEM, SLK_EINVAL, SLK_ERANGE = 0, -5, -12, -22, -34
 
 LOSS_KINDS = {'pointwise': 0, 'bpr': 1, 'hinge': 2, 'adaptive_hinge': 3,
@@ -124,6 +124,11 @@ _PROTOTYPES = {
                                             C.c_void_p]),
     'slk_shard_user_pass_adaptive': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_shard_target_scores': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_shard_rank_counts': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_shard_scores': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'slk_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'slk_profile_read': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'slk_profile_reset': (C.c_int, [C.c_void_p]),
@@ -525,6 +530,26 @@ class Engine(object):
     def shard_item_pass(self, tables, optim, minibatch, d_grad_in, stream=0):
         self._check(self._lib.slk_shard_item_pass(self._ctx, C.byref(tables), C.byref(optim), int(minibatch),
                                                   d_grad_in, stream))
+
+    # -- evaluation of a row-sharded model (include/spotlight_hip.h: slk_shard_target_scores / _rank_counts / _scores) --
+    def shard_target_scores(self, tables, d_rep, d_rbias, n_groups, d_row_group, d_row_target_local, n_rows, d_exc_off,
+                            d_exc_items_local, d_st_out, stream=0):
+        """d_st_out[r]: the score of row r's target where `tables` (this rank's shard) owns it, else -inf; combine the ranks
+        with all_reduce(MAX)."""
+        self._check(self._lib.slk_shard_target_scores(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_groups), d_row_group,
+                                                      d_row_target_local, int(n_rows), d_exc_off, d_exc_items_local, d_st_out,
+                                                      stream))
+
+    def shard_rank_counts(self, tables, d_rep, d_rbias, n_groups, d_row_group, d_st, n_rows, d_exc_off, d_exc_items_local,
+                          d_gt_out, d_eq_out, stream=0):
+        """int64 counts of this rank's items scoring above / equal to the GLOBAL target scores d_st; combine the ranks with
+        all_reduce(SUM)."""
+        self._check(self._lib.slk_shard_rank_counts(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_groups), d_row_group, d_st,
+                                                    int(n_rows), d_exc_off, d_exc_items_local, d_gt_out, d_eq_out, stream))
+
+    def shard_scores(self, tables, d_rep, d_rbias, n_rows, d_out, stream=0):
+        """d_out[n_rows][tables.num_items]: the representations' scores against this rank's item rows."""
+        self._check(self._lib.slk_shard_scores(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_rows), d_out, stream))
 
     # -- measurement -------------------------------------------------------------------
     def profile_enable(self, on=True):

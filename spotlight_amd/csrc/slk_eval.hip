@@ -396,17 +396,21 @@ __global__ __launch_bounds__(256) void k_score_rows(slk_gemm_args a) {
 
 // st[r] = score(representation of row r, its target item) on the vector unit (the same chain); a target that is on its own
 // group's exclusion list scores -FLT_MAX, as the reference's `predictions[excluded] = FLOAT_MAX` makes it
-template <int VEC, int G>
+// SHARD (slk_shard_target_scores): V / bi are ONE RANK's rows and tgt[r] is the target's LOCAL row, or -1 where another rank
+// owns it (any row outside [0, I) is treated so): such a row scores -INFINITY, the identity of the ranks' MAX
+template <int VEC, int G, bool SHARD>
 __global__ __launch_bounds__(256) void k_rank_target_scores(const float *rep, const float *rbias, const int64_t *rowmap,
                                                             const int64_t *gmap, const float *V, const float *bi, slk_bloom_dev ib, int D,
-                                                            const int64_t *tgt, const int64_t *exc_off, const int64_t *exc_items,
-                                                            int64_t n_rows, float *st) {
+                                                            int64_t I, const int64_t *tgt, const int64_t *exc_off,
+                                                            const int64_t *exc_items, int64_t n_rows, float *st) {
     constexpr int GPB = 256 / G;
     const int lane = threadIdx.x % G, grp = threadIdx.x / G;
     const int d0 = lane * VEC;
     const bool on = d0 < D;
     for (int64_t r = (int64_t)blockIdx.x * GPB + grp; r < n_rows; r += (int64_t)gridDim.x * GPB) {
-        const int64_t g = rowmap ? rowmap[r] : r, item = tgt[r];
+        const int64_t g = rowmap ? rowmap[r] : r;
+        const bool owned = !SHARD || (tgt[r] >= 0 && tgt[r] < I);
+        const int64_t item = owned ? tgt[r] : 0;  // (a row that is not owned walks row 0: the group's lanes stay together)
         const int64_t src = gmap ? gmap[g] : g;
         const slk_vec<VEC> x = on ? slk_vload<VEC>(rep + (size_t)src * D + d0) : slk_vzero<VEC>();
         const slk_vec<VEC> y = slk_emb_vec<VEC>(V, ib, (uint32_t)item, D, d0, on);
@@ -417,6 +421,7 @@ __global__ __launch_bounds__(256) void k_rank_target_scores(const float *rep, co
             for (int64_t e = exc_off[g] + lane; e < exc_off[g + 1]; e += G) hit |= (exc_items[e] == item) ? 1ull : 0ull;
             if (slk_group_or<G>(hit)) sc = -FLT_MAX;
         }
+        if (SHARD && !owned) sc = -INFINITY;
         if (lane == 0) st[r] = sc;
     }
 }
@@ -458,6 +463,15 @@ __global__ __launch_bounds__(256) void k_rank_final(const unsigned *gt, const un
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
         const double g = (double)gt[r] + (dgt ? (double)dgt[r] : 0.0), e = (double)eq[r] + (deq ? (double)deq[r] : 0.0);
         rank[r] = g + (e + 1.0) * 0.5;
+    }
+}
+
+// the sharded form of k_rank_final: ONE RANK's share of the two counts, corrections applied, widened for the ranks' SUM
+__global__ __launch_bounds__(256) void k_rank_counts_out(const unsigned *gt, const unsigned *eq, const int *dgt, const int *deq,
+                                                         int64_t n_rows, int64_t *gt_out, int64_t *eq_out) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
+        gt_out[r] = (int64_t)gt[r] + (dgt ? (int64_t)dgt[r] : 0);
+        eq_out[r] = (int64_t)eq[r] + (deq ? (int64_t)deq[r] : 0);
     }
 }
 
@@ -663,28 +677,63 @@ SLK_EXPORT int slk_poolnet_scores(slk_ctx *ctx, const slk_tables *tables, const 
 }
 
 // Fused ranking: rank_out[r] = rankdata(-scores(group row_group[r]) with the group's exclusions pushed last)[row_target[r]]
-// without a score matrix: the target scores (vector unit), ONE counting sweep of the item table per 64 rows (matrix cores),
-// the exclusion lists' corrections (vector unit).  rep / rbias: the groups' representations.
-static int rank_fused(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
-                      const int64_t *gmap, const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows, const int64_t *d_exc_off,
-                      const int64_t *d_exc_items, double *d_rank_out, hipStream_t s) {
+// without a score matrix, in three stages: the target scores (vector unit), ONE counting sweep of the item table per 64 rows
+// (matrix cores) with the exclusion lists' corrections (vector unit), and the counts' way out.  rep / rbias: the groups'
+// representations.  The one-device entries run the stages back to back (rank_fused); the sharded entries run the first two on
+// ONE RANK's item rows with a collective of the host's after each (slk_shard_target_scores / slk_shard_rank_counts).
+struct rank_counters {
+    unsigned *gt, *eq;  // the sweep's counts
+    int *dgt, *deq;     // the exclusion lists' signed corrections
+};
+
+static int rank_scratch(slk_ctx *ctx, int64_t n_rows, bool want_st, float **st, rank_counters *c) {
     int rc;
-    if ((rc = slk_ensure(ctx, ctx->extra[EV_ST], (size_t)n_rows * 4))) return rc;
+    if (want_st) {
+        if ((rc = slk_ensure(ctx, ctx->extra[EV_ST], (size_t)n_rows * 4))) return rc;
+        *st = (float *)ctx->extra[EV_ST].p;
+    }
     if ((rc = slk_ensure(ctx, ctx->extra[EV_CNT], (size_t)n_rows * 16))) return rc;
-    float *st = (float *)ctx->extra[EV_ST].p;
-    unsigned *gt = (unsigned *)ctx->extra[EV_CNT].p, *eq = gt + n_rows;
-    int *dgt = (int *)(eq + n_rows), *deq = dgt + n_rows;
-    SLK_HIP(ctx, hipMemsetAsync(gt, 0, (size_t)n_rows * 8, s));
+    c->gt = (unsigned *)ctx->extra[EV_CNT].p;
+    c->eq = c->gt + n_rows;
+    c->dgt = (int *)(c->eq + n_rows);
+    c->deq = c->dgt + n_rows;
+    return SLK_OK;
+}
+
+// stage 1: st[r] = the score of row r's target (-FLT_MAX where the target is on its group's exclusion list; `shard`: -INFINITY
+// where d_row_target[r] is no row of these tables)
+static int rank_target_scores(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
+                              const int64_t *gmap, const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows,
+                              const int64_t *d_exc_off, const int64_t *d_exc_items, bool shard, float *st, hipStream_t s) {
     slk_bloom_dev ibd;
     slk_bloom_to_dev(tables->item_bloom, &ibd);
     const float *V = (const float *)tables->d_param[1], *bi = (const float *)tables->d_param[3];
     const int D = tables->dim;
-#define SLK_TGT(V_, G_)                                                                                             \
-    hipLaunchKernelGGL((k_rank_target_scores<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, rep, \
-                       rbias, d_row_group, gmap, V, bi, ibd, D, d_row_target, d_exc_off, d_exc_items, n_rows, st)
+    const int64_t I = tables->num_items;
+#define SLK_TGT(V_, G_)                                                                                                      \
+    do {                                                                                                                     \
+        if (shard)                                                                                                           \
+            hipLaunchKernelGGL((k_rank_target_scores<V_, G_, true>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)),      \
+                               dim3(256), 0, s, rep, rbias, d_row_group, gmap, V, bi, ibd, D, I, d_row_target, d_exc_off,    \
+                               d_exc_items, n_rows, st);                                                                     \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((k_rank_target_scores<V_, G_, false>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)),     \
+                               dim3(256), 0, s, rep, rbias, d_row_group, gmap, V, bi, ibd, D, I, d_row_target, d_exc_off,    \
+                               d_exc_items, n_rows, st);                                                                     \
+    } while (0)
     SLK_FOR_LAYOUT(vec, g, SLK_TGT);
 #undef SLK_TGT
     SLK_LAUNCH_CHECK(ctx, "k_rank_target_scores");
+    return SLK_OK;
+}
+
+// stage 2: c.gt / c.eq = #{items of these tables scoring > / == st[r]}; c.dgt / c.deq (written iff d_exc_off): what pushing the
+// exclusion list's items of these tables to -FLT_MAX changes of them
+static int rank_counts(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
+                       const int64_t *gmap, const int64_t *d_row_group, int64_t n_rows, const int64_t *d_exc_off,
+                       const int64_t *d_exc_items, const float *st, const rank_counters &c, hipStream_t s) {
+    int rc;
+    SLK_HIP(ctx, hipMemsetAsync(c.gt, 0, (size_t)n_rows * 8, s));
     slk_gemm_args a;
     memset(&a, 0, sizeof(a));
     a.rep = rep;
@@ -693,20 +742,38 @@ static int rank_fused(slk_ctx *ctx, const slk_tables *tables, int vec, int g, co
     a.gmap = gmap;
     a.R = n_rows;
     a.st = st;
-    a.gt = gt;
-    a.eq = eq;
+    a.gt = c.gt;
+    a.eq = c.eq;
     if ((rc = eval_gemm(ctx, tables, a, true, s))) return rc;
     if (d_exc_off) {
+        slk_bloom_dev ibd;
+        slk_bloom_to_dev(tables->item_bloom, &ibd);
+        const float *V = (const float *)tables->d_param[1], *bi = (const float *)tables->d_param[3];
+        const int D = tables->dim;
 #define SLK_EXC(V_, G_)                                                                                             \
     hipLaunchKernelGGL((k_rank_exclusions<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, rep,   \
-                       rbias, d_row_group, gmap, V, bi, ibd, D, d_exc_off, d_exc_items, (const float *)st, n_rows, dgt, deq)
+                       rbias, d_row_group, gmap, V, bi, ibd, D, d_exc_off, d_exc_items, st, n_rows, c.dgt, c.deq)
         SLK_FOR_LAYOUT(vec, g, SLK_EXC);
 #undef SLK_EXC
         SLK_LAUNCH_CHECK(ctx, "k_rank_exclusions");
     }
-    hipLaunchKernelGGL(k_rank_final, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)gt,
-                       (const unsigned *)eq, d_exc_off ? (const int *)dgt : (const int *)nullptr,
-                       d_exc_off ? (const int *)deq : (const int *)nullptr, n_rows, d_rank_out);
+    return SLK_OK;
+}
+
+static int rank_fused(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
+                      const int64_t *gmap, const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows, const int64_t *d_exc_off,
+                      const int64_t *d_exc_items, double *d_rank_out, hipStream_t s) {
+    int rc;
+    float *st = nullptr;
+    rank_counters c;
+    if ((rc = rank_scratch(ctx, n_rows, true, &st, &c))) return rc;
+    if ((rc = rank_target_scores(ctx, tables, vec, g, rep, rbias, gmap, d_row_group, d_row_target, n_rows, d_exc_off, d_exc_items,
+                                 false, st, s)))
+        return rc;
+    if ((rc = rank_counts(ctx, tables, vec, g, rep, rbias, gmap, d_row_group, n_rows, d_exc_off, d_exc_items, st, c, s))) return rc;
+    hipLaunchKernelGGL(k_rank_final, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)c.gt,
+                       (const unsigned *)c.eq, d_exc_off ? (const int *)c.dgt : (const int *)nullptr,
+                       d_exc_off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_rank_out);
     SLK_LAUNCH_CHECK(ctx, "k_rank_final");
     return SLK_OK;
 }
@@ -761,6 +828,92 @@ SLK_EXPORT int slk_poolnet_rank(slk_ctx *ctx, const slk_tables *tables, const in
     float *rep;
     if ((rc = eval_seq_rows(ctx, tables, vec, g, d_group_sequences, n_groups, seq_len, &rep, s))) return rc;
     rc = rank_fused(ctx, tables, vec, g, rep, nullptr, nullptr, d_row_group, d_row_target, n_rows, d_exc_off, d_exc_items, d_rank_out, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+// ---- sharded evaluation: one rank's item rows against caller-supplied representations ----------------------------------------
+// (include/spotlight_hip.h: the item side of `local` only -- a group's user row usually lives on another rank, so the
+// representations come as dense arrays.  The counts are integers: their sum over the ranks is the one-device count.)
+static int check_shard_eval(slk_ctx *ctx, const char *who, const slk_tables *local, const float *d_rep, const float *d_rbias,
+                            int64_t n_rep, int *vec, int *g) {
+    if (local && local->item_bloom)
+        return slk_fail(ctx, SLK_EINVAL, "%s: a bloom item table cannot be row-sharded (plain tables only)", who);
+    int rc;
+    if ((rc = slk_check_tables(ctx, local, 10u, vec, g))) return rc;  // (item side: refuses item biases inside a bias-shadow scope)
+    if (n_rep < 0) return slk_fail(ctx, SLK_EINVAL, "%s: bad arguments", who);
+    if (n_rep > 0 && (!d_rep || !d_rbias)) return slk_fail(ctx, SLK_EINVAL, "%s: the representations (d_rep / d_rbias) are NULL", who);
+    return SLK_OK;
+}
+
+SLK_EXPORT int slk_shard_target_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias,
+                                       int64_t n_groups, const int64_t *d_row_group, const int64_t *d_row_target_local,
+                                       int64_t n_rows, const int64_t *d_exc_off, const int64_t *d_exc_items_local,
+                                       float *d_st_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_shard_eval(ctx, "slk_shard_target_scores", local, d_rep, d_rbias, n_groups, &vec, &g))) return rc;
+    if (n_rows < 0 || (n_rows > 0 && (!d_row_group || !d_row_target_local || !d_st_out)))
+        return slk_fail(ctx, SLK_EINVAL, "slk_shard_target_scores: bad arguments");
+    if (n_rows > 0 && n_groups == 0) return slk_fail(ctx, SLK_EINVAL, "slk_shard_target_scores: rows without groups");
+    if (n_rows == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    rc = rank_target_scores(ctx, local, vec, g, d_rep, d_rbias, nullptr, d_row_group, d_row_target_local, n_rows, d_exc_off,
+                            d_exc_items_local, true, d_st_out, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+SLK_EXPORT int slk_shard_rank_counts(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias,
+                                     int64_t n_groups, const int64_t *d_row_group, const float *d_st, int64_t n_rows,
+                                     const int64_t *d_exc_off, const int64_t *d_exc_items_local, int64_t *d_gt_out,
+                                     int64_t *d_eq_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_shard_eval(ctx, "slk_shard_rank_counts", local, d_rep, d_rbias, n_groups, &vec, &g))) return rc;
+    if (n_rows < 0 || (n_rows > 0 && (!d_row_group || !d_st || !d_gt_out || !d_eq_out)))
+        return slk_fail(ctx, SLK_EINVAL, "slk_shard_rank_counts: bad arguments");
+    if (n_rows > 0 && n_groups == 0) return slk_fail(ctx, SLK_EINVAL, "slk_shard_rank_counts: rows without groups");
+    if (n_rows == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    rank_counters c;
+    if ((rc = rank_scratch(ctx, n_rows, false, nullptr, &c))) return rc;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    rc = rank_counts(ctx, local, vec, g, d_rep, d_rbias, nullptr, d_row_group, n_rows, d_exc_off, d_exc_items_local, d_st, c, s);
+    if (rc == SLK_OK) {
+        hipLaunchKernelGGL(k_rank_counts_out, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)c.gt,
+                           (const unsigned *)c.eq, d_exc_off ? (const int *)c.dgt : (const int *)nullptr,
+                           d_exc_off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_gt_out, d_eq_out);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = slk_fail(ctx, SLK_EIO, "launch of %s failed: %s", "k_rank_counts_out", hipGetErrorString(e));
+    }
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+SLK_EXPORT int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
+                                float *d_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_shard_eval(ctx, "slk_shard_scores", local, d_rep, d_rbias, n_rows, &vec, &g))) return rc;
+    if (n_rows > 0 && !d_out) return slk_fail(ctx, SLK_EINVAL, "slk_shard_scores: bad arguments");
+    if (n_rows == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    slk_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    a.rep = d_rep;
+    a.rbias = d_rbias;
+    a.R = n_rows;
+    a.out = d_out;
+    rc = eval_gemm(ctx, local, a, false, s);
     slk_prof_end(ctx, s);
     return rc;
 }

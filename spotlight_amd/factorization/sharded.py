@@ -334,12 +334,11 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
 
     All four losses (adaptive hinge: a score phase and a selection over the whole minibatch in front of the user pass,
     ShardedBilinearTrainer.run_chunk).  Restriction of the exchange path: plain (non-bloom) tables.
-    """
 
-    # evaluation.mrr_score's one-device fast path scores against whole tables; this model's are local shards
-    # indexed by local rows, so ranking goes through predict() (rows assembled from their owners)
-    _batch_scores = None
-    _fused_ranks = None
+    Evaluation runs shard by shard as well: evaluation.mrr_score (_fused_ranks), precision_recall_score (_batch_scores) and
+    predict(user) sweep every rank's own item rows and combine the ranks' target scores (MAX), integer counts (SUM) or score
+    columns (all-gather) -- the one-device model's results bit for bit; only the users' rows travel.
+    """
 
     def __init__(self, *args, **kwargs):
         self._group = kwargs.pop('group', None)
@@ -472,10 +471,103 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         dist.all_reduce(out, group=self._group)  # every row has exactly one owner
         return out
 
+    def _local_item_tables(self):
+        """slk_tables over this rank's item shard (the sharded evaluation entries read the item side only), or None where
+        the shard is empty (num_items < world)."""
+        w = self._net.tables()
+        if w[1].shape[0] == 0:
+            return None
+        return _native.make_tables([None, w[1].data_ptr(), None, w[3].data_ptr()], 0, w[1].shape[0], w[1].shape[1])
+
+    def _user_representations(self, users, device):
+        """(rep [n, D], rbias [n]) of the users, assembled from their owners: the only table data evaluation puts on the wire."""
+        rows = self._fetch_rows(0, 2, users, device)
+        D = rows.shape[1] - 1
+        return rows[:, :D].contiguous(), rows[:, D].contiguous()
+
+    def _shard_scores(self, users):
+        """[n, num_items] device tensor, row r == the one-device model's predict(users[r]), bit for bit: every rank scores its
+        own item rows (slk_shard_scores), the shards are all-gathered (padded to the largest) and interleaved.  No item row
+        travels."""
+        world, rank = self._world, self._rank
+        device = self._net.tables()[0].device
+        n, I = len(users), self._num_items
+        rep, rbias = self._user_representations(users, device)
+        tb = self._local_item_tables()
+        n_loc = tb.num_items if tb is not None else 0
+        loc = torch.empty((n, n_loc), dtype=torch.float32, device=device)
+        if tb is not None:
+            _host._engine_for(device).shard_scores(tb, rep.data_ptr(), rbias.data_ptr(), n, loc.data_ptr(), _host._stream_for(device))
+        if world == 1:
+            return loc
+        mine = torch.zeros((n, local_rows(I, world, 0)), dtype=torch.float32, device=device)  # padded to the largest shard
+        mine[:, :n_loc] = loc
+        shards = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(shards, mine, group=self._group)
+        out = torch.empty((n, I), dtype=torch.float32, device=device)
+        for r in range(world):
+            out[:, r::world] = shards[r][:, :local_rows(I, world, r)]
+        return out
+
+    def _batch_scores(self, user_ids):
+        """[len(user_ids), num_items] device tensor: row r == predict(user_ids[r]) (evaluation.precision_recall_score's
+        device top-k route); every rank makes the same call and gets the same rows."""
+        users = np.ascontiguousarray(np.asarray(user_ids).reshape(-1), dtype=np.int64)
+        self._check_input(users, None, allow_items_none=True)
+        self._net.train(False)
+        return self._shard_scores(users)
+
+    def _fused_ranks(self, user_ids, row_group, row_target, exc_off, exc_items):
+        """Average ranks of the rows' target items (evaluation.mrr_score's fast path), shard by shard: every rank sweeps its own
+        item rows only (slk_shard_target_scores, slk_shard_rank_counts) and two small collectives -- MAX over the target scores,
+        SUM over the integer counts -- make the result the one-device model's, bit for bit.  Every rank makes the same call."""
+        users = np.ascontiguousarray(np.asarray(user_ids).reshape(-1), dtype=np.int64)
+        self._check_input(users, None, allow_items_none=True)
+        self._net.train(False)
+        world, rank = self._world, self._rank
+        device = self._net.tables()[0].device
+        n_groups, n_rows = len(users), len(row_group)
+        rep, rbias = self._user_representations(users, device)
+        row_group = np.ascontiguousarray(np.asarray(row_group).astype(np.int64))
+        row_target = np.asarray(row_target).astype(np.int64)
+        # this rank's view of the ids: a target's local row where it is owned here (else -1), each group's excluded items that
+        # live here as local rows (the CSR rebuilt over them)
+        tgt_local = np.where(row_target % world == rank, row_target // world, -1)
+        eo = ei = None
+        if exc_off is not None:
+            exc_off, exc_items = np.asarray(exc_off).astype(np.int64), np.asarray(exc_items).astype(np.int64)
+            here = exc_items % world == rank
+            eo = np.concatenate([[0], np.cumsum(here)])[exc_off].astype(np.int64)
+            ei = (exc_items[here] // world).astype(np.int64)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        st = torch.full((n_rows,), float('-inf'), dtype=torch.float32, device=device)
+        counts = torch.zeros((2, n_rows), dtype=torch.int64, device=device)
+        tb = self._local_item_tables()
+        if tb is not None:
+            engine, stream = _host._engine_for(device), _host._stream_for(device)
+            d_rg, d_tl = dev(row_group), dev(tgt_local)
+            d_eo, d_ei = (dev(eo), dev(ei)) if eo is not None else (None, None)
+            p_eo = d_eo.data_ptr() if d_eo is not None else None
+            p_ei = d_ei.data_ptr() if d_ei is not None else None
+            engine.shard_target_scores(tb, rep.data_ptr(), rbias.data_ptr(), n_groups, d_rg.data_ptr(), d_tl.data_ptr(), n_rows,
+                                       p_eo, p_ei, st.data_ptr(), stream)
+        if world > 1:
+            dist.all_reduce(st, op=dist.ReduceOp.MAX, group=self._group)  # one owner per target: exact
+        if tb is not None:
+            engine.shard_rank_counts(tb, rep.data_ptr(), rbias.data_ptr(), n_groups, d_rg.data_ptr(), st.data_ptr(), n_rows,
+                                     p_eo, p_ei, counts[0].data_ptr(), counts[1].data_ptr(), stream)
+        if world > 1:
+            dist.all_reduce(counts, group=self._group)  # integers: exact
+        ranks = counts[0].double() + (counts[1].double() + 1.0) * 0.5  # scipy's 'average'
+        return ranks.cpu().numpy()
+
     def predict(self, user_ids, item_ids=None):
         self._check_input(user_ids, item_ids, allow_items_none=True)
         self._net.train(False)
         users, items, n = _predict_process_ids(user_ids, item_ids, self._num_items)
+        if items is None and users.size == 1:
+            # one user against every item: each rank scores its own shard, no item row travels
+            return self._shard_scores(users).cpu().numpy().flatten()
         if items is None:
             items = np.arange(n, dtype=np.int64)
         device = self._net.tables()[0].device
