@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SLK_ABI_VERSION 13
+#define SLK_ABI_VERSION 14
 
 #define SLK_OK 0
 #define SLK_EIO (-5)
@@ -194,7 +194,10 @@ const char *slk_last_error(const slk_ctx *ctx); /* ctx may be NULL: last create 
  *   "user_grid_own_occ"   0 (default): the user pass launches at most as many workgroups per CU as the form with the most registers
  *                         (plain, latency-bound, long runs, ping-pong) holds resident; 1: as the form it launches does (measured:
  *                         no gain at C2, -12 % on the C5 shard, profiles/r06_w_*; same tables, the fp32 loss sums associate by
- *                         workgroup) */
+ *                         workgroup)
+ *   "topk_items_per_wg"   slk_*_topk: items one workgroup of the selecting sweep covers (rounded up to whole blocks of 128; 0,
+ *                         the default: cut as the scoring sweep cuts them, ~4 workgroups per CU).  A test and measurement
+ *                         switch: the top-k order is total, the result is the same under every value */
 int slk_ctx_set_option(slk_ctx *ctx, const char *name, int64_t value);
 /* The current value of an option (ABI 9): lets a caller change an option for one piece of work and restore it afterwards --
  * a ctx is shared by every model of a process on its device (spotlight_amd/_native.py: `with engine.options(...)`). */
@@ -591,6 +594,45 @@ int slk_shard_rank_counts(slk_ctx *ctx, const slk_tables *local, const float *d_
                           const int64_t *d_exc_items_local, int64_t *d_gt_out, int64_t *d_eq_out, void *stream);
 int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
                      float *d_out, void *stream);
+
+/* Top-k recommendation (ABI 14): the k best items of every row (a user / a sequence / a representation), selected INSIDE the
+ * sweep that scores them -- one pass over the item table per tile of 64 rows (32 where k is large), every score consumed as it
+ * leaves the accumulators: no score matrix.
+ *
+ * THE ORDER.  For a row and k >= 1 the result is the first k of the row's ELIGIBLE items in this order:
+ *   1. score descending, compared as floats (-0.0 == +0.0);
+ *   2. ties: item id ascending;
+ *   3. a NaN score orders below every number (below -inf); NaNs among themselves by id ascending.
+ * This is a total order: the result does not depend on the grid, the chunking of the item table ("topk_items_per_wg"), the
+ * arrival order of atomics or -- for the sharded entry, whose per-rank results the host merges by the same order -- the world
+ * size.
+ *   eligible  every item that is not on the row's exclusion list.  d_exc_off[n_rows + 1] / d_exc_items: CSR, row r's list is
+ *             d_exc_items[d_exc_off[r] .. d_exc_off[r + 1]), SORTED ascending and DISTINCT (the sweep binary-searches it);
+ *             d_exc_off NULL: no exclusions.  Offsets that decrease or start below 0 are refused (checked on the device: the one
+ *             host wait of a call with exclusions).  An excluded item never appears in the output.
+ *   padding   a row with fewer than k eligible items ends in item = -1, score = -INFINITY.
+ *   scores    the bits predict() / slk_*_scores return for that (row, item): the same k-ordered fmaf chain, the biases added in
+ *             the same order -- except that a zero may lose its sign and that every NaN comes back as the quiet NaN 0x7fc00000.
+ *   outputs   int64 d_items_out[n_rows][k], float d_scores_out[n_rows][k], both best first.
+ * 1 <= k <= SLK_TOPK_K_MAX (a caller that wants more sorts score rows: spotlight_amd's recommend() does).  Item ids must fit
+ * 32 bits.  Scratch is the ctx's: n_rows * chunks * k keys of 8 bytes per launch, rows processed in tiles so that it stays
+ * below 64 MB (more only where "topk_items_per_wg" forces thousands of chunks); nothing table-sized, nothing retained.
+ *   slk_bilinear_topk  rows = users (BilinearNet: (dot + bu) + bi)
+ *   slk_poolnet_topk   rows = sequences [n_seq][seq_len] (PoolNet: bi + dot)
+ *   slk_shard_topk     ONE RANK's item rows (`local`, as slk_shard_scores reads it: plain item tables only) against the dense
+ *                      representations d_rep[n_rows][dim] / d_rbias[n_rows]; d_exc_items_local and d_items_local_out are LOCAL
+ *                      item rows (global id = local * world + rank).  The ranks' [world][n_rows][k] candidates merged by the
+ *                      order above ARE the one-device result. */
+#define SLK_TOPK_K_MAX 128
+int slk_bilinear_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_users, int64_t n_users, int64_t k,
+                      const int64_t *d_exc_off, const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out,
+                      void *stream);
+int slk_poolnet_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_sequences, int64_t n_seq, int64_t seq_len,
+                     int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out,
+                     void *stream);
+int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows, int64_t k,
+                   const int64_t *d_exc_off, const int64_t *d_exc_items_local, int64_t *d_items_local_out, float *d_scores_out,
+                   void *stream);
 
 /* Measurement support (the reference has none; examples/bloom_embeddings/performance.py
  * times fit() with time.time()): when enabled, every launch of the engine's kernels is

@@ -13,7 +13,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libspotlight_hip.so')
 
-SLK_ABI_VERSION = 13
+SLK_ABI_VERSION = 14
+TOPK_K_MAX = 128  # include/spotlight_hip.h: SLK_TOPK_K_MAX
 SLK_OK, SLK_EIO, SLK_ENOMEM, SLK_EINVAL, SLK_ERANGE = 0, -5, -12, -22, -34
 
 LOSS_KINDS = {'pointwise': 0, 'bpr': 1, 'hinge': 2, 'adaptive_hinge': 3,
@@ -129,6 +130,12 @@ _PROTOTYPES = {
     'slk_shard_rank_counts': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_shard_scores': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'slk_bilinear_topk': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_poolnet_topk': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_shard_topk': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'slk_profile_read': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'slk_profile_reset': (C.c_int, [C.c_void_p]),
@@ -551,6 +558,25 @@ class Engine(object):
         """d_out[n_rows][tables.num_items]: the representations' scores against this rank's item rows."""
         self._check(self._lib.slk_shard_scores(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_rows), d_out, stream))
 
+    # -- top-k recommendation (include/spotlight_hip.h: slk_*_topk, "THE ORDER") ---------------
+    def bilinear_topk(self, tables, d_users, n_users, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, stream=0):
+        """d_items_out[n_users][k] (int64) / d_scores_out[n_users][k]: every user's k best eligible items, best first (score
+        descending, ties to the smaller id, NaN last; padded with -1 / -inf); d_exc_off / d_exc_items: CSR of sorted, distinct
+        excluded items per user, or None."""
+        self._check(self._lib.slk_bilinear_topk(self._ctx, C.byref(tables), d_users, int(n_users), int(k), d_exc_off, d_exc_items,
+                                                d_items_out, d_scores_out, stream))
+
+    def poolnet_topk(self, tables, d_sequences, n_seq, seq_len, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, stream=0):
+        self._check(self._lib.slk_poolnet_topk(self._ctx, C.byref(tables), d_sequences, int(n_seq), int(seq_len), int(k),
+                                               d_exc_off, d_exc_items, d_items_out, d_scores_out, stream))
+
+    def shard_topk(self, tables, d_rep, d_rbias, n_rows, k, d_exc_off, d_exc_items_local, d_items_local_out, d_scores_out,
+                   stream=0):
+        """The k best of this rank's item rows (`tables`: its shard) per representation, as LOCAL rows; merge the ranks'
+        candidates by the same order (merge_topk)."""
+        self._check(self._lib.slk_shard_topk(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_rows), int(k), d_exc_off,
+                                             d_exc_items_local, d_items_local_out, d_scores_out, stream))
+
     # -- measurement -------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self._lib.slk_profile_enable(self._ctx, 1 if on else 0))
@@ -594,6 +620,29 @@ class Engine(object):
             self._check(self._lib.slk_profile_read(self._ctx, cls, C.byref(n), C.byref(ms)))
             out[name] = (int(n.value), float(ms.value))
         return out
+
+
+def topk_order(scores, items=None):
+    """The permutation that puts a row's (score, item) pairs into the order of include/spotlight_hip.h ("THE ORDER"): score
+    descending (-0.0 == +0.0), ties to the smaller id, NaN after every number."""
+    scores = np.asarray(scores, dtype=np.float32)
+    items = np.arange(scores.shape[0]) if items is None else np.asarray(items)
+    nan = np.isnan(scores)
+    return np.lexsort((items, -np.where(nan, np.float32(0), scores).astype(np.float64), nan))
+
+
+def merge_topk(items, scores, k):
+    """[n, m] candidate lists (item -1 = padding) -> the [n, k] best by topk_order, padded with -1 / -inf."""
+    items, scores = np.asarray(items), np.asarray(scores, dtype=np.float32)
+    n = items.shape[0]
+    out_i = np.full((n, k), -1, dtype=np.int64)
+    out_s = np.full((n, k), -np.inf, dtype=np.float32)
+    for r in range(n):
+        live = np.nonzero(items[r] >= 0)[0]
+        o = live[topk_order(scores[r][live], items[r][live])][:k]
+        out_i[r, :len(o)] = items[r][o]
+        out_s[r, :len(o)] = scores[r][o]
+    return out_i, out_s
 
 
 BLOOM_SEEDS = (179424941, 179425457, 179425907, 179426369,

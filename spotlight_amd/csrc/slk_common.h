@@ -48,6 +48,15 @@
 #define SLK_WAVE_SYNC() __syncthreads()
 #endif
 
+// The same for ONE wavefront of a larger workgroup (the top-k compaction of slk_eval.hip: one wave per row, the other waves
+// busy with other rows or not at all): nothing to wait for on the GPU either; in the test harness a switch point of the wave
+// alone -- a shuffle -- because the waves of the workgroup do not pass it the same number of times.
+#if defined(__HIPCC__)
+#define SLK_SUBWAVE_SYNC() SLK_WAVE_SYNC()
+#else
+#define SLK_SUBWAVE_SYNC() ((void)__shfl(0, 0))
+#endif
+
 // Marks the next plain kernel launch as one whose workgroups wait for each other inside the kernel (grid barrier): all of
 // them must be resident at once.  On the GPU that is a property of the launch geometry (at most one wavefront-sized
 // workgroup per CU, slk_epoch.hip) and the marker is empty; the test harness, which otherwise executes one block at a
@@ -188,6 +197,8 @@ struct slk_ctx {
                                       // the four forms' -- measured, profiles/r06_w_*: 7 instead of 6 workgroups per CU buys the C2 pass nothing
                                       // (0.285-0.287 against 0.283 ms) and costs the C5 shard's 12 % (0.393 against 0.350: more rows in flight
                                       // over a 64-GB working set = more translation misses)
+    int64_t opt_topk_items_per_wg = 0;  // slk_*_topk: items per workgroup of the selecting sweep (0: as the scoring sweep cuts them); a test /
+                                      // measurement switch, the result does not depend on it
     int opt_user_bias_zero_hint = 1;  // 1: honour SLK_TABLES_USER_BIAS_ZERO (0: fetch the user biases regardless -- A/B and test switch)
     int64_t opt_record_nt_min_bytes = (int64_t)192 << 20;  // records of a minibatch from this size on are stored non-temporally
                                    // (slk_bilinear.hip::do_passes; 0: never)

@@ -93,7 +93,12 @@ struct slk_gemm_args {
     float *out;                   // WRITE: [R][I]
     const float *st;              // COUNT: the row's target score
     unsigned *gt, *eq;            // COUNT: per-row counts (atomicAdd)
+    int k, cap;                   // SELECT: keys kept per row, candidate slots per row in LDS (>= k + SLK_GEMM_IB)
+    const int64_t *exc_off, *exc_items;  // SELECT: row r's excluded items, sorted and distinct (CSR; exc_off nullptr: none)
+    unsigned long long *cand;     // SELECT: [R][gridDim.x][k] keys, 0 = empty
 };
+
+enum { SLK_GEMM_WRITE = 0, SLK_GEMM_COUNT = 1, SLK_GEMM_SELECT = 2 };  // what the sweep does with a score
 
 #if defined(__HIPCC__)
 typedef float slk_f32x16 __attribute__((ext_vector_type(16)));
@@ -112,10 +117,95 @@ __device__ __forceinline__ float slk_gemm_item_elem(const float *V, const slk_bl
     return v;
 }
 
-template <int MT, bool COUNT, bool VEC4, bool AREG>
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// MODE SELECT (slk_*_topk): the k best items of every row, by the total order of include/spotlight_hip.h -- score descending
+// (-0.0 == +0.0), ties to the smaller id, NaN below every number.  One 64-bit key carries the order: the high word is the
+// score's orderable bits (0 = NaN, then -inf .. +inf ascending), the low word ~item, so "better" is one unsigned compare and no
+// two items of a row share a key; key 0 is no item at all (an empty slot: item -1, score -inf).  Every row of the tile keeps in
+// LDS a threshold key (the k-th best key seen so far, 0 until there are k), a count and `cap` candidate slots.  A lane whose
+// score beats its row's threshold looks the item up in the row's exclusion list (binary search: only survivors pay for it) and
+// takes a slot with one LDS atomic.  A block of the sweep adds at most SLK_GEMM_IB candidates to a row, so a row whose count
+// is at most cap - SLK_GEMM_IB cannot overflow in the next block; a row above that is compacted first: one wave sorts its
+// slots (a bitonic network whose comparators all point the same way, so the slots past `cap` may stay virtual), the threshold
+// becomes the k-th key and the count k.  A stale threshold is a lower bound of the true k-th key: it only lets more candidates in,
+// the result does not depend on when rows are compacted, on the chunking or on the order of the atomics.
+// ---------------------------------------------------------------------------------------------------------------------------
+typedef unsigned long long slk_key;
+
+__device__ __forceinline__ unsigned slk_topk_hi(float sc) {
+    if (sc != sc) return 0u;
+    if (sc == 0.0f) return 0x80000000u;  // both zeros
+    unsigned b;
+    memcpy(&b, &sc, 4);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float slk_topk_score(unsigned hi) {
+    const unsigned b = hi == 0u ? 0x7fc00000u : ((hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi);
+    float sc;
+    memcpy(&sc, &b, 4);
+    return sc;
+}
+
+__device__ __forceinline__ bool slk_topk_excluded(const int64_t *list, int64_t lo, int64_t end, int64_t item) {
+    int64_t hi = end;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (list[mid] < item) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && list[lo] == item;
+}
+
+// ONE WAVE: sorts c[0, cap) descending (the slots from `count` on are emptied first) and keeps the k best: *thr = the k-th key
+// (0 while there are fewer), *cnt = min(count, k).  Every lane of the wave calls it with the same arguments.
+__device__ inline void slk_topk_compact(slk_key *c, unsigned count, int k, int cap, int lane, slk_key *thr, unsigned *cnt) {
+    for (int i = (int)count + lane; i < cap; i += 64) c[i] = 0ull;
+    int n = 64;
+    while (n < cap) n <<= 1;
+    SLK_SUBWAVE_SYNC();
+    for (int kk = 2; kk <= n; kk <<= 1) {
+        // two sorted runs of kk / 2: element i against its mirror image in the pair of runs ...
+        for (int t = lane; t < n / 2; t += 64) {
+            const int b = t / (kk / 2), off = t - b * (kk / 2);
+            const int i = b * kk + off, p = b * kk + kk - 1 - off;
+            if (p < cap) {  // (a slot past cap is empty and stays so: the better key goes to the smaller index)
+                const slk_key x = c[i], y = c[p];
+                if (y > x) {
+                    c[i] = y;
+                    c[p] = x;
+                }
+            }
+        }
+        SLK_SUBWAVE_SYNC();
+        // ... then the half-cleaners of every run
+        for (int j = kk >> 2; j >= 1; j >>= 1) {
+            for (int t = lane; t < n / 2; t += 64) {
+                const int i = (t / j) * 2 * j + (t % j), p = i + j;
+                if (p < cap) {
+                    const slk_key x = c[i], y = c[p];
+                    if (y > x) {
+                        c[i] = y;
+                        c[p] = x;
+                    }
+                }
+            }
+            SLK_SUBWAVE_SYNC();
+        }
+    }
+    if (lane == 0) {
+        *thr = count >= (unsigned)k ? c[k - 1] : 0ull;
+        *cnt = count < (unsigned)k ? count : (unsigned)k;
+    }
+    SLK_SUBWAVE_SYNC();
+}
+
+template <int MT, int MODE, bool VEC4, bool AREG>
 __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm_args a) {  // (two workgroups per CU by LDS footprint, eval_gemm: 2 waves per SIMD)
     constexpr int RT = 32 * MT, IB = SLK_GEMM_IB, KC = SLK_GEMM_KC, KS = SLK_GEMM_KS;
     constexpr int BREG = VEC4 ? IB * KC / 256 : 1;  // staged floats per thread (plain tables of dim % 4 == 0)
+    constexpr bool COUNT = MODE == SLK_GEMM_COUNT, SELECT = MODE == SLK_GEMM_SELECT;
     HIP_DYNAMIC_SHARED(float, lds)
     float *sA = lds;                      // [RT][KS]
     float *sB = sA + RT * KS;             // [IB][KS]
@@ -123,6 +213,11 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
     float *s_st = s_rb + RT;              // [RT]
     unsigned *s_gt = reinterpret_cast<unsigned *>(s_st + RT);  // [RT]
     unsigned *s_eq = s_gt + RT;           // [RT]
+    // SELECT: per row the threshold key, the window of its exclusion list, the candidate count and the candidates
+    slk_key *s_thr = reinterpret_cast<slk_key *>(s_eq + RT);   // [RT]  ((RT + IB) * KS + 4 * RT floats: a multiple of 8 bytes)
+    int64_t *s_eo = reinterpret_cast<int64_t *>(s_thr + RT);   // [RT][2]
+    slk_key *s_cand = reinterpret_cast<slk_key *>(s_eo + 2 * RT);  // [RT][a.cap]
+    unsigned *s_cnt = reinterpret_cast<unsigned *>(s_cand + (SELECT ? (size_t)RT * a.cap : 0));  // [RT]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D;
     const int64_t r0 = (int64_t)blockIdx.y * RT;
@@ -139,6 +234,12 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
             s_st[t] = live ? a.st[r0 + t] : 0.0f;
             s_gt[t] = 0u;
             s_eq[t] = 0u;
+        }
+        if (SELECT) {
+            s_thr[t] = live ? 0ull : ~0ull;  // (a row past the last one takes no candidate)
+            s_cnt[t] = 0u;
+            s_eo[2 * t] = (live && a.exc_off) ? a.exc_off[r0 + t] : 0;
+            s_eo[2 * t + 1] = (live && a.exc_off) ? a.exc_off[r0 + t + 1] : 0;
         }
     }
     // the representations' chunk [kc, kc + KC) -> sA (zero beyond D and beyond the last row)
@@ -262,7 +363,7 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
         const bool live = item < i_end;
         const float bias = live ? a.bi[item] : 0.0f;
         // (WRITE: this lane's output column; the row offsets below are wave-uniform multiples of the row stride)
-        float *ocol = COUNT ? nullptr : a.out + (size_t)(r0 + 4 * (lane >> 5)) * a.I + item;
+        float *ocol = MODE != SLK_GEMM_WRITE ? nullptr : a.out + (size_t)(r0 + 4 * (lane >> 5)) * a.I + item;
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -277,10 +378,42 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
                 if (COUNT) {
                     const float t = s_st[row];
                     cnt[m * 16 + v] += (live && sc > t ? 1u : 0u) + (live && sc == t ? 0x10000u : 0u);
+                } else if (SELECT) {
+                    // the high words alone turn nearly every score away; an equal high word is a tie: the ids decide
+                    const unsigned hi = slk_topk_hi(sc);
+                    if (live && hi >= (unsigned)(s_thr[row] >> 32)) {
+                        const slk_key key = ((slk_key)hi << 32) | (slk_key)(~(unsigned)item);
+                        if (key > s_thr[row] && !slk_topk_excluded(a.exc_items, s_eo[2 * row], s_eo[2 * row + 1], item))
+                            s_cand[(size_t)row * a.cap + atomicAdd(&s_cnt[row], 1u)] = key;
+                    }
                 } else if (live && r0 + row < a.R) {
                     ocol[(size_t)row_a * a.I] = sc;
                 }
             }
+        if (SELECT) {
+            __syncthreads();  // the block's candidates are in
+            for (int row = wave; row < RT; row += 4) {
+                const unsigned c = s_cnt[row];
+                if (c > (unsigned)(a.cap - IB)) slk_topk_compact(s_cand + (size_t)row * a.cap, c, a.k, a.cap, lane, &s_thr[row], &s_cnt[row]);
+            }
+            // (the next block's epilogue is two barriers away)
+        }
+    }
+    if (SELECT) {
+        // the chunk's at most k keys of every row -> a.cand[row][chunk][k]
+        __syncthreads();
+        for (int row = wave; row < RT; row += 4) {
+            unsigned c = s_cnt[row];
+            slk_key *cs = s_cand + (size_t)row * a.cap;
+            if (c > (unsigned)a.k) {
+                slk_topk_compact(cs, c, a.k, a.cap, lane, &s_thr[row], &s_cnt[row]);
+                c = (unsigned)a.k;
+            }
+            if (r0 + row < a.R) {
+                slk_key *dst = a.cand + ((size_t)(r0 + row) * gridDim.x + blockIdx.x) * a.k;
+                for (int i = lane; i < a.k; i += 64) dst[i] = i < (int)c ? cs[i] : 0ull;
+            }
+        }
     }
     if (COUNT) {
         __syncthreads();
@@ -510,13 +643,55 @@ __global__ __launch_bounds__(256) void k_eval_rank(const float *scores, int64_t 
     }
 }
 
+
+// SELECT, second stage: row r's n_chunks * k keys -> its k best, best first, decoded.  One wave per row: the keys stream
+// through the same threshold + candidate buffer + compaction as in the sweep.
+#define SLK_TOPK_MERGE_CAP 256
+__global__ __launch_bounds__(256) void k_topk_merge(const slk_key *cand, int64_t n_rows, int64_t per_row, int k, int64_t *items_out,
+                                                    float *scores_out) {
+    constexpr int CAP = SLK_TOPK_MERGE_CAP;
+    __shared__ slk_key s_c[4][CAP];
+    __shared__ slk_key s_thr[4];
+    __shared__ unsigned s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n_rows; r += (int64_t)gridDim.x * 4) {
+        if (lane == 0) {
+            s_thr[wave] = 0ull;
+            s_cnt[wave] = 0u;
+        }
+        SLK_SUBWAVE_SYNC();
+        const slk_key *src = cand + (size_t)r * per_row;
+        for (int64_t base = 0; base < per_row; base += 64) {
+            const slk_key key = base + lane < per_row ? src[base + lane] : 0ull;
+            if (key > s_thr[wave]) s_c[wave][atomicAdd(&s_cnt[wave], 1u)] = key;
+            SLK_SUBWAVE_SYNC();
+            const unsigned c = s_cnt[wave];
+            SLK_SUBWAVE_SYNC();  // (every lane has read the count before the next piece's first candidate moves it)
+            if (c > (unsigned)(CAP - 64)) slk_topk_compact(s_c[wave], c, k, CAP, lane, &s_thr[wave], &s_cnt[wave]);
+        }
+        slk_topk_compact(s_c[wave], s_cnt[wave], k, CAP, lane, &s_thr[wave], &s_cnt[wave]);  // sorted, empty slots last
+        for (int i = lane; i < k; i += 64) {
+            const slk_key key = s_c[wave][i];
+            items_out[(size_t)r * k + i] = key ? (int64_t)(~(unsigned)key) : (int64_t)-1;
+            scores_out[(size_t)r * k + i] = key ? slk_topk_score((unsigned)(key >> 32)) : -INFINITY;
+        }
+        SLK_SUBWAVE_SYNC();
+    }
+}
+
+// *bad = 1 unless 0 <= exc_off[0] <= exc_off[1] <= ... <= exc_off[n]
+__global__ __launch_bounds__(256) void k_topk_check_offsets(const int64_t *exc_off, int64_t n, int *bad) {
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256)
+        if (exc_off[g] < 0 || exc_off[g + 1] < exc_off[g]) *bad = 1;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-enum { EV_ST = 37, EV_CNT = 39 };  // ctx->extra slots of the fused ranking (24, 25: the representations)
+enum { EV_ST = 37, EV_CNT = 39, EV_TOPK = 48, EV_TOPK_FLAG = 49 };  // ctx->extra slots of the fused ranking (24, 25: the representations)
 
 typedef void (*gemm_fn)(slk_gemm_args);
 
 // areg: the representations' operand in registers for the whole sweep (plain tables of dim <= 64)
-template <bool COUNT>
+template <int COUNT>  // (the sweep's MODE)
 static gemm_fn gemm_kernel(int mt, bool vec4, bool areg) {
     if (areg) return mt == 1 ? k_score_gemm<1, COUNT, true, true> : k_score_gemm<2, COUNT, true, true>;
     if (mt == 1) return vec4 ? k_score_gemm<1, COUNT, true, false> : k_score_gemm<1, COUNT, false, false>;
@@ -572,7 +747,7 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
     const size_t half_lds = ctx->lds_per_cu / 2 - 256;
     if (lds < half_lds && half_lds <= ctx->lds_per_block) lds = half_lds;
     const bool areg = vec4 && a.D <= SLK_GEMM_KC;
-    gemm_fn fn = count ? gemm_kernel<true>(mt, vec4, areg) : gemm_kernel<false>(mt, vec4, areg);
+    gemm_fn fn = count ? gemm_kernel<SLK_GEMM_COUNT>(mt, vec4, areg) : gemm_kernel<SLK_GEMM_WRITE>(mt, vec4, areg);
     if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, dim3((unsigned)chunks, (unsigned)row_tiles), dim3(256), lds, s, a);
     SLK_LAUNCH_CHECK(ctx, "k_score_gemm");
@@ -914,6 +1089,170 @@ SLK_EXPORT int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const flo
     a.R = n_rows;
     a.out = d_out;
     rc = eval_gemm(ctx, local, a, false, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+
+// ---- top-k: MODE SELECT of the sweep + k_topk_merge ------------------------------------------------------------------------------
+#define SLK_TOPK_SCRATCH_BYTES ((size_t)64 << 20)  // candidate scratch of one launch (rows are processed in tiles to stay below it)
+
+static size_t topk_lds(int mt, int cap) {
+    return ((size_t)(32 * mt + SLK_GEMM_IB) * SLK_GEMM_KS + 4 * 32 * mt) * 4 + (size_t)32 * mt * ((size_t)cap * 8 + 32);
+}
+
+// rep / rbias / gmap: the rows' representations as eval_gemm takes them (row r = group r); d_exc_off[R + 1]
+static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, const float *rep, const float *rbias,
+                    const int64_t *gmap, int64_t R, int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items,
+                    int64_t *d_items_out, float *d_scores_out, hipStream_t s) {
+    int rc;
+    const int64_t I = tables->num_items;
+    const int D = tables->dim;
+    if (I <= 0) return slk_fail(ctx, SLK_EINVAL, "%s: no items", who);
+    if (I >= ((int64_t)1 << 32) - 1) return slk_fail(ctx, SLK_EINVAL, "%s: %lld items, ids must fit 32 bits", who, (long long)I);
+    if (d_exc_off) {
+        // the offsets index d_exc_items inside the sweep: checked here, the one host wait of the call
+        if ((rc = slk_ensure(ctx, ctx->extra[EV_TOPK_FLAG], sizeof(int)))) return rc;
+        int *d_bad = (int *)ctx->extra[EV_TOPK_FLAG].p, h_bad = 0;
+        SLK_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_topk_check_offsets, dim3(slk_grid_for(ctx, (size_t)R, 256)), dim3(256), 0, s, d_exc_off, R, d_bad);
+        SLK_LAUNCH_CHECK(ctx, "k_topk_check_offsets");
+        SLK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        SLK_HIP(ctx, hipStreamSynchronize(s));
+        if (h_bad) return slk_fail(ctx, SLK_EINVAL, "%s: d_exc_off is not sorted (offsets must start at >= 0 and never decrease)", who);
+    }
+    // the row tile: 64 rows where their candidate slots fit beside the operands (small k), else 32; every slot the LDS has
+    // left (up to 512) goes to the candidates: the more slack above k + SLK_GEMM_IB, the fewer compactions
+    int mt = 0, cap = 0;
+    for (int m = R > 32 ? 2 : 1; m >= 1 && !mt; --m) {
+        const size_t base = topk_lds(m, 0);
+        if (ctx->lds_per_block <= base) continue;
+        size_t c = (ctx->lds_per_block - base) / ((size_t)32 * m * 8);
+        if (c > 512) c = 512;
+        if ((int64_t)c >= k + SLK_GEMM_IB) {
+            mt = m;
+            cap = (int)c;
+        }
+    }
+    if (!mt) return slk_fail(ctx, SLK_EINVAL, "%s: k = %lld does not fit the device's %zu B of LDS per workgroup", who, (long long)k, ctx->lds_per_block);
+    const int RT = 32 * mt;
+    slk_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    slk_bloom_to_dev(tables->item_bloom, &a.ib);
+    a.V = (const float *)tables->d_param[1];
+    a.bi = (const float *)tables->d_param[3];
+    a.D = D;
+    a.I = I;
+    a.k = (int)k;
+    a.cap = cap;
+    a.exc_items = d_exc_items;
+    const bool vec4 = a.ib.n_hash == 0 && D % 4 == 0;
+    const bool areg = vec4 && D <= SLK_GEMM_KC;
+    gemm_fn fn = gemm_kernel<SLK_GEMM_SELECT>(mt, vec4, areg);
+    const size_t lds = topk_lds(mt, cap);
+    if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int64_t row_step = 16384;
+    for (int64_t r_lo = 0; r_lo < R; r_lo += row_step) {
+        int64_t n = R - r_lo < row_step ? R - r_lo : row_step;
+        // item chunks: the option's, else as eval_gemm cuts them (~4 workgroups per CU over all row tiles)
+        int64_t per = ctx->opt_topk_items_per_wg;
+        if (per <= 0) {
+            const int64_t row_tiles = (n + RT - 1) / RT;
+            int64_t want = ((row_tiles == 1 ? 2 : 4) * (int64_t)ctx->num_cus + row_tiles - 1) / row_tiles;
+            per = (I + want - 1) / want;
+        }
+        per = (per + SLK_GEMM_IB - 1) / SLK_GEMM_IB * SLK_GEMM_IB;
+        const int64_t chunks = (I + per - 1) / per;
+        if (chunks > 0x7fffffff) return slk_fail(ctx, SLK_EINVAL, "%s: %lld item chunks per row tile", who, (long long)chunks);
+        // rows of this launch: as many whole tiles as keep the candidate scratch bounded
+        const size_t row_bytes = (size_t)chunks * (size_t)k * 8;
+        if ((size_t)n * row_bytes > SLK_TOPK_SCRATCH_BYTES) {
+            int64_t fit = (int64_t)(SLK_TOPK_SCRATCH_BYTES / row_bytes) / RT * RT;
+            if (fit < RT) fit = RT;
+            if (fit < n) n = fit;
+            row_step = n;
+        }
+        if ((rc = slk_ensure(ctx, ctx->extra[EV_TOPK], (size_t)n * row_bytes))) return rc;
+        a.cand = (slk_key *)ctx->extra[EV_TOPK].p;
+        a.items_per_wg = per;
+        a.R = n;
+        a.rep = gmap ? rep : rep + (size_t)r_lo * D;
+        a.rbias = (gmap || !rbias) ? rbias : rbias + r_lo;
+        a.gmap = gmap ? gmap + r_lo : nullptr;
+        a.exc_off = d_exc_off ? d_exc_off + r_lo : nullptr;
+        hipLaunchKernelGGL(fn, dim3((unsigned)chunks, (unsigned)((n + RT - 1) / RT)), dim3(256), lds, s, a);
+        SLK_LAUNCH_CHECK(ctx, "k_score_gemm<SELECT>");
+        hipLaunchKernelGGL(k_topk_merge, dim3(slk_grid_for(ctx, (size_t)n, 4)), dim3(256), 0, s, (const slk_key *)a.cand, n,
+                           chunks * k, (int)k, d_items_out + (size_t)r_lo * k, d_scores_out + (size_t)r_lo * k);
+        SLK_LAUNCH_CHECK(ctx, "k_topk_merge");
+    }
+    return SLK_OK;
+}
+
+static int check_topk_args(slk_ctx *ctx, const char *who, int64_t n_rows, const void *rows, int64_t k, const int64_t *d_exc_off,
+                           const int64_t *d_exc_items, const int64_t *d_items_out, const float *d_scores_out) {
+    if (k < 1) return slk_fail(ctx, SLK_EINVAL, "%s: k = %lld, at least 1", who, (long long)k);
+    if (k > SLK_TOPK_K_MAX) return slk_fail(ctx, SLK_EINVAL, "%s: k = %lld, at most SLK_TOPK_K_MAX = %d", who, (long long)k, SLK_TOPK_K_MAX);
+    if (n_rows < 0 || (n_rows > 0 && !rows) || (d_exc_off && !d_exc_items)) return slk_fail(ctx, SLK_EINVAL, "%s: bad arguments", who);
+    if (n_rows > 0 && (!d_items_out || !d_scores_out)) return slk_fail(ctx, SLK_EINVAL, "%s: the outputs (d_items_out / d_scores_out) are NULL", who);
+    return SLK_OK;
+}
+
+SLK_EXPORT int slk_bilinear_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_users, int64_t n_users, int64_t k,
+                                 const int64_t *d_exc_off, const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out,
+                                 void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = slk_check_tables(ctx, tables, 15u, &vec, &g))) return rc;
+    if ((rc = check_topk_args(ctx, "slk_bilinear_topk", n_users, d_users, k, d_exc_off, d_exc_items, d_items_out, d_scores_out))) return rc;
+    if (n_users == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    const float *rep, *rbias;
+    const int64_t *gmap;
+    if ((rc = eval_user_rows(ctx, tables, vec, g, d_users, n_users, &rep, &rbias, &gmap, s))) return rc;
+    rc = topk_run(ctx, "slk_bilinear_topk", tables, rep, rbias, gmap, n_users, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+SLK_EXPORT int slk_poolnet_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_sequences, int64_t n_seq, int64_t seq_len,
+                                int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items, int64_t *d_items_out,
+                                float *d_scores_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = slk_check_tables(ctx, tables, 10u, &vec, &g))) return rc;
+    if (seq_len < 1) return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_topk: seq_len %lld", (long long)seq_len);
+    if ((rc = check_topk_args(ctx, "slk_poolnet_topk", n_seq, d_sequences, k, d_exc_off, d_exc_items, d_items_out, d_scores_out))) return rc;
+    if (n_seq == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    float *rep;
+    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_sequences, n_seq, seq_len, &rep, s))) return rc;
+    rc = topk_run(ctx, "slk_poolnet_topk", tables, rep, nullptr, nullptr, n_seq, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+SLK_EXPORT int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
+                              int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items_local, int64_t *d_items_local_out,
+                              float *d_scores_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_shard_eval(ctx, "slk_shard_topk", local, d_rep, d_rbias, n_rows, &vec, &g))) return rc;
+    if ((rc = check_topk_args(ctx, "slk_shard_topk", n_rows, d_rep, k, d_exc_off, d_exc_items_local, d_items_local_out, d_scores_out)))
+        return rc;
+    if (n_rows == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    rc = topk_run(ctx, "slk_shard_topk", local, d_rep, d_rbias, nullptr, n_rows, k, d_exc_off, d_exc_items_local, d_items_local_out,
+                  d_scores_out, s);
     slk_prof_end(ctx, s);
     return rc;
 }

@@ -801,6 +801,56 @@ class ImplicitFactorizationModel(object):
                                           d_ei.data_ptr() if d_ei is not None else None, ranks.data_ptr(), _stream_for(device))
         return ranks.cpu().numpy()
 
+    def _is_custom_net(self):
+        return getattr(self, '_autograd_route', False) and not isinstance(self._net, BilinearNet)
+
+    def _recommend_prepare(self, user_ids, k, exclude):
+        from spotlight_amd import recommend as _rec
+        k = _rec.check_k(k)
+        users = np.ascontiguousarray(np.asarray(user_ids).reshape(-1), dtype=np.int64)
+        if users.size:
+            self._check_input(users, None, allow_items_none=True)
+        self._net.train(False)
+        return _rec, users, k, _rec.exclusion_lists(exclude, users, self._num_items)
+
+    def _recommend_generic(self, users, k, lists):
+        """Score rows a tile at a time, sorted on the host (spotlight_amd/recommend.py: generic_topk)."""
+        from spotlight_amd import recommend as _rec
+        if self._is_custom_net():  # a custom module scores with its own forward: one predict() per user
+            rows = lambda us: np.stack([self.predict(int(u)) for u in us])
+        else:
+            rows = lambda us: self._batch_scores(us).cpu().numpy()
+        return _rec.generic_topk(rows, users, self._num_items, k, lists)
+
+    def recommend(self, user_ids, k=10, exclude=None):
+        """The k best items of every user: (items int64 [n, k], scores float32 [n, k]), best first.
+
+        Order: score descending (-0.0 == +0.0), ties to the smaller item id, a NaN score after every number -- a total order,
+        so the result is the same on every route, grid and world size.  `exclude`: None, an Interactions / scipy sparse matrix
+        (row u = the items to hide from user u: the `train` of mrr_score) or one index array per user; an excluded item never
+        appears.  A user with fewer than k eligible items gets item -1 / score -inf in the tail.  Every score is the bits
+        predict() returns for that (user, item), except that a zero may lose its sign (and a NaN its payload).
+
+        k <= TOPK_K_MAX (128) selects inside the scoring sweep (csrc/slk_eval.hip, slk_bilinear_topk: one pass over the item
+        table per 64 users, no score matrix, no library kernel); a larger k, or a custom representation module, sorts score
+        rows a tile at a time."""
+        _rec, users, k, lists = self._recommend_prepare(user_ids, k, exclude)
+        if not users.size:
+            return _rec.empty_result(k)
+        if k > _rec.TOPK_K_MAX or self._is_custom_net():
+            return self._recommend_generic(users, k, lists)
+        device = self._net.tables()[0].device
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        d_users = dev(users)
+        d_eo, d_ei = [dev(a) for a in _rec.csr_of(lists)] if lists is not None else (None, None)
+        items = torch.empty((users.size, k), dtype=torch.int64, device=device)
+        scores = torch.empty((users.size, k), dtype=torch.float32, device=device)
+        _engine_for(device).bilinear_topk(self._slk_tables(), d_users.data_ptr(), users.size, k,
+                                          d_eo.data_ptr() if d_eo is not None else None,
+                                          d_ei.data_ptr() if d_ei is not None else None, items.data_ptr(), scores.data_ptr(),
+                                          _stream_for(device))
+        return items.cpu().numpy(), scores.cpu().numpy()
+
     def _batch_scores(self, user_ids):
         """[len(user_ids), num_items] device tensor: row r == predict(user_ids[r]) (bit-identical), a
         tile of users per pass over the item table (csrc/slk_eval.hip); used by evaluation.mrr_score."""

@@ -561,6 +561,41 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         ranks = counts[0].double() + (counts[1].double() + 1.0) * 0.5  # scipy's 'average'
         return ranks.cpu().numpy()
 
+    def recommend(self, user_ids, k=10, exclude=None):
+        """ImplicitFactorizationModel.recommend, shard by shard: every rank selects the k best of ITS item rows against the
+        users' representations (slk_shard_topk; no score row, no item row on the wire), the [world][n][k] candidates are
+        all-gathered as global ids and merged by the same total order -- the arrays of the one-device model.  Every rank makes
+        the same call and gets the same arrays."""
+        _rec, users, k, lists = self._recommend_prepare(user_ids, k, exclude)
+        if not users.size:
+            return _rec.empty_result(k)
+        if k > _rec.TOPK_K_MAX:
+            return self._recommend_generic(users, k, lists)
+        world, rank = self._world, self._rank
+        device = self._net.tables()[0].device
+        n = users.size
+        rep, rbias = self._user_representations(users, device)
+        items = torch.full((n, k), -1, dtype=torch.int64, device=device)
+        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=device)
+        tb = self._local_item_tables()
+        if tb is not None:
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            d_eo = d_ei = None
+            if lists is not None:  # each user's excluded items that live here, as local rows
+                d_eo, d_ei = [dev(a) for a in _rec.csr_of([x[x % world == rank] // world for x in lists])]
+            _host._engine_for(device).shard_topk(tb, rep.data_ptr(), rbias.data_ptr(), n, k,
+                                                 d_eo.data_ptr() if d_eo is not None else None,
+                                                 d_ei.data_ptr() if d_ei is not None else None, items.data_ptr(),
+                                                 scores.data_ptr(), _host._stream_for(device))
+            items = torch.where(items >= 0, items * world + rank, items)
+        if world == 1:
+            return items.cpu().numpy(), scores.cpu().numpy()
+        all_items = [torch.empty_like(items) for _ in range(world)]
+        all_scores = [torch.empty_like(scores) for _ in range(world)]
+        dist.all_gather(all_items, items, group=self._group)
+        dist.all_gather(all_scores, scores, group=self._group)
+        return _rec.merge_topk(torch.cat(all_items, dim=1).cpu().numpy(), torch.cat(all_scores, dim=1).cpu().numpy(), k)
+
     def predict(self, user_ids, item_ids=None):
         self._check_input(user_ids, item_ids, allow_items_none=True)
         self._net.train(False)

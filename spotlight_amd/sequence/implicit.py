@@ -348,6 +348,35 @@ class ImplicitSequenceModel(object):
                                                _host._stream_for(device))
         return ranks.cpu().numpy()
 
+    def recommend(self, sequences, k=10, exclude_preceding=False):
+        """The k best next items of every sequence: (items int64 [n, k], scores float32 [n, k]), best first, in the order of
+        ImplicitFactorizationModel.recommend (score descending, ties to the smaller id, NaN last; padded with -1 / -inf).
+        `exclude_preceding`: a sequence's own items (as sequence_mrr_score hides them: the padding item included) never appear.
+        A PoolNet with k <= TOPK_K_MAX selects inside the scoring sweep (slk_poolnet_topk: no score matrix); any other
+        representation, or a larger k, sorts score rows a tile at a time."""
+        from spotlight_amd import recommend as _rec
+        k = _rec.check_k(k)
+        self._net.train(False)
+        sequences = np.atleast_2d(sequences)
+        if not sequences.size:
+            return _rec.empty_result(k)
+        self._check_input(sequences)
+        seqs = np.ascontiguousarray(sequences.astype(np.int64))
+        lists = _rec.exclusion_lists([row for row in seqs], seqs, self._num_items) if exclude_preceding else None
+        if k > _rec.TOPK_K_MAX or not isinstance(self._net, PoolNet):
+            return _rec.generic_topk(lambda s: self._batch_scores(s).cpu().numpy(), seqs, self._num_items, k, lists)
+        device = self._net.tables()[0].device
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        d_seqs = dev(seqs)
+        d_eo, d_ei = [dev(a) for a in _rec.csr_of(lists)] if lists is not None else (None, None)
+        items = torch.empty((seqs.shape[0], k), dtype=torch.int64, device=device)
+        scores = torch.empty((seqs.shape[0], k), dtype=torch.float32, device=device)
+        _host._engine_for(device).poolnet_topk(self._slk_tables(), d_seqs.data_ptr(), seqs.shape[0], seqs.shape[1], k,
+                                               d_eo.data_ptr() if d_eo is not None else None,
+                                               d_ei.data_ptr() if d_ei is not None else None, items.data_ptr(),
+                                               scores.data_ptr(), _host._stream_for(device))
+        return items.cpu().numpy(), scores.cpu().numpy()
+
     def _batch_scores(self, sequences):
         """[n_sequences, num_items] device tensor: row r == predict(sequences[r]) (bit-identical), a tile
         of sequences per pass over the item table (csrc/slk_eval.hip); used by evaluation.sequence_mrr_score."""
