@@ -197,7 +197,12 @@ const char *slk_last_error(const slk_ctx *ctx); /* ctx may be NULL: last create 
  *                         workgroup)
  *   "topk_items_per_wg"   slk_*_topk: items one workgroup of the selecting sweep covers (rounded up to whole blocks of 128; 0,
  *                         the default: cut as the scoring sweep cuts them, ~4 workgroups per CU).  A test and measurement
- *                         switch: the top-k order is total, the result is the same under every value */
+ *                         switch: the top-k order is total, the result is the same under every value
+ *   "eval_items_per_wg"   slk_*_scores, slk_*_rank, slk_*_predict over every item, slk_shard_scores, slk_shard_rank_counts: items one
+ *                         workgroup of the writing / counting sweep covers (rounded up to whole blocks: 128 items, 256 in the
+ *                         streaming form that serves up to 8 rows of a plain table with dim % 4 == 0; never more than 2^22, which
+ *                         the packed rank counters can hold; 0, the default: cut from the device's CU count).  A test and measurement
+ *                         switch: every score and every rank is the same under every value.  slk_*_topk keeps its own option */
 int slk_ctx_set_option(slk_ctx *ctx, const char *name, int64_t value);
 /* The current value of an option (ABI 9): lets a caller change an option for one piece of work and restore it afterwards --
  * a ctx is shared by every model of a process on its device (spotlight_amd/_native.py: `with engine.options(...)`). */

@@ -250,10 +250,12 @@ const slk_opt_desc slk_options[] = {
 #undef SLK_OPT
 // An option of the EVALUATION side: it has nothing to say about training, so it is no row of the table above (whose rows
 // tests/engine_checks.py trains under, one by one); that the top-k result does not depend on it is tests/topk_checks.py's
-// chunking invariance.
+// chunking invariance, that scores and ranks do not depend on "eval_items_per_wg" is tests/sweep_checks.py.
 const slk_opt_desc slk_eval_options[] = {
     {"topk_items_per_wg", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_topk_items_per_wg; },
      [](slk_ctx *c, int64_t v) { c->opt_topk_items_per_wg = v; }},
+    {"eval_items_per_wg", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_eval_items_per_wg; },
+     [](slk_ctx *c, int64_t v) { c->opt_eval_items_per_wg = v; }},
 };
 const slk_opt_desc *slk_find_option(const char *name) {
     for (const slk_opt_desc &d : slk_options)

@@ -199,6 +199,9 @@ struct slk_ctx {
                                       // over a 64-GB working set = more translation misses)
     int64_t opt_topk_items_per_wg = 0;  // slk_*_topk: items per workgroup of the selecting sweep (0: as the scoring sweep cuts them); a test /
                                       // measurement switch, the result does not depend on it
+    int64_t opt_eval_items_per_wg = 0;  // slk_*_scores / slk_*_rank / predict over every item / slk_shard_scores / _rank_counts: items per
+                                      // workgroup of the writing and the counting sweep (0: cut by the device's CU count, eval_gemm);
+                                      // the same kind of switch
     int opt_user_bias_zero_hint = 1;  // 1: honour SLK_TABLES_USER_BIAS_ZERO (0: fetch the user biases regardless -- A/B and test switch)
     int64_t opt_record_nt_min_bytes = (int64_t)192 << 20;  // records of a minibatch from this size on are stored non-temporally
                                    // (slk_bilinear.hip::do_passes; 0: never)

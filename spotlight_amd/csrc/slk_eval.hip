@@ -708,7 +708,9 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
     if (a.R <= 0 || a.I <= 0) return SLK_OK;
     if (!count && a.R <= 8 && a.ib.n_hash == 0 && a.D % 4 == 0) {
         // a handful of rows: the streaming form (k_score_rows), two workgroups per CU each sweeping whole blocks of 256 items
-        int64_t per = (a.I + 2 * (int64_t)ctx->num_cus - 1) / (2 * (int64_t)ctx->num_cus);
+        // (option "eval_items_per_wg": the cut given, a test and measurement switch)
+        int64_t per = ctx->opt_eval_items_per_wg;
+        if (per <= 0) per = (a.I + 2 * (int64_t)ctx->num_cus - 1) / (2 * (int64_t)ctx->num_cus);
         per = (per + SLK_ROWS_IB - 1) / SLK_ROWS_IB * SLK_ROWS_IB;
         a.items_per_wg = per;
         const int nr = a.R == 1 ? 1 : (a.R == 2 ? 2 : (a.R <= 4 ? 4 : 8));
@@ -731,7 +733,8 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
     // SLK_GEMM_IB items
     int64_t want = ((row_tiles == 1 ? 2 : 4) * (int64_t)ctx->num_cus + row_tiles - 1) / row_tiles;
     if (want < 1) want = 1;
-    int64_t per = (a.I + want - 1) / want;
+    int64_t per = ctx->opt_eval_items_per_wg;  // (0: the automatic cut)
+    if (per <= 0) per = (a.I + want - 1) / want;
     per = (per + SLK_GEMM_IB - 1) / SLK_GEMM_IB * SLK_GEMM_IB;
     if (per > ((int64_t)1 << 22)) per = (int64_t)1 << 22;  // (the packed per-lane counters hold 2^16 - 1 columns: 2^23 items)
     a.items_per_wg = per;
