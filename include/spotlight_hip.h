@@ -330,7 +330,8 @@ int slk_bias_shadow_abort(slk_ctx *ctx);
  * Same arithmetic in the same order: tables bit-identical to training without the scope.
  *   - tables->d_param[0] is a MIX of current and superseded rows inside the scope; _end copies the rows whose current copy is
  *     the ctx's back into it.  Every call that names it other than slk_bilinear_train / _prefetch / _reserve (predict, scores,
- *     ranks, the row-sharded calls) is refused with SLK_EINVAL until then.
+ *     ranks, the row-sharded calls) is refused with SLK_EINVAL until then -- the neighbour entries (slk_rows_inv_norm,
+ *     slk_neighbors_topk / _scores), which take the array as a bare pointer, included.
  *   - slk_bilinear_train inside the scope: the pair losses (pointwise, bpr, hinge) over plain tables with a row-sparse optimizer
  *     (Adagrad, SparseAdam, SGD), any minibatch size, on the launch path (not the persistent kernel).  Adaptive hinge,
  *     explicit feedback, dense optimizers and other tables are refused with SLK_EINVAL -- the scope belongs to one model's
@@ -638,6 +639,41 @@ int slk_poolnet_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_se
 int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows, int64_t k,
                    const int64_t *d_exc_off, const int64_t *d_exc_items_local, int64_t *d_items_local_out, float *d_scores_out,
                    void *stream);
+
+/* Neighbours in the embedding space (added to ABI 14: three new entries, nothing existing changes, SLK_ABI_VERSION stays -- a
+ * library without them fails to bind on the missing symbols): "rows like this one" by cosine or by dot product, selected inside the same sweep
+ * -- no [n_q x n_table_rows] score matrix.  All three entries take raw device pointers, so one code path serves an item table,
+ * a user table, one rank's shard of either and a materialised BloomEmbedding table ([n][dim], id j's row = the sum of its
+ * hashed rows).  No biases are read.
+ *
+ *   slk_rows_inv_norm    d_out[r] = 1.0f / sqrtf(s_r), s_r = sum_d x[r][d]^2 formed as the d-ordered chain s = fmaf(x_d, x_d, s)
+ *                        from 0 (every build and every caller defines the same bits: a rank that holds a copy of a row gets
+ *                        the value the row's owner gets).  s_r == 0 exactly gives 0.0f -- a zero row scores 0 against
+ *                        everything, never NaN; a NaN or inf s_r propagates (NaN / 0).  n_rows == 0 is a no-op.
+ *   slk_neighbors_topk   the k best rows of d_table[n_table_rows][dim] for every dense query row d_queries[n_q][dim].
+ *   slk_neighbors_scores d_out[q * n_table_rows + j]: the score rows whose selection slk_neighbors_topk returns, bit for bit (the
+ *                        route for k > SLK_TOPK_K_MAX).
+ *
+ * THE SCORE of (q, j), with acc the k-ordered chain acc = fmaf(query[q][d], table[j][d], acc), d = 0 .. dim-1, from 0 -- the chain
+ * of every other sweep of this header:
+ *   d_tscale == NULL and d_qscale == NULL   ("dot")     acc
+ *   both given                               ("cosine")  (acc * d_qscale[q]) * d_tscale[j], in that order -- with
+ *                                                        d_qscale[n_q] / d_tscale[n_table_rows] the rows' slk_rows_inv_norm
+ *   exactly one given                                    refused.
+ * Order, padding (-1 / -INFINITY), NaN handling, the exclusion lists (d_exc_off[n_q + 1] / d_exc_items: sorted, distinct TABLE
+ * rows per query; a query that is itself a table row is excluded by listing it), 1 <= k <= SLK_TOPK_K_MAX, the 32-bit id limit,
+ * the scratch bound and "topk_items_per_wg" are exactly those of slk_*_topk above ("THE ORDER").
+ * Refused with SLK_EINVAL: NULL table / queries / outputs, k out of range, n_table_rows <= 0 or >= 2^32 - 1, dim < 1 (or a dim
+ * the row layouts do not serve: dim % 4 == 0 and <= 256, or dim <= 64), unsorted offsets, and -- as for every other reader of that
+ * array (slk_user_pingpong_begin above) -- a d_table or d_queries that is the user table of an open ping-pong scope: it holds a mix of
+ * current and superseded rows until slk_user_pingpong_end.  Nothing is retained; scratch is the ctx's (shared with slk_*_topk);
+ * profiled under SLK_K_SCORE. */
+int slk_rows_inv_norm(slk_ctx *ctx, const float *d_table, int64_t n_rows, int64_t dim, float *d_out, void *stream);
+int slk_neighbors_topk(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
+                       const float *d_queries, const float *d_qscale, int64_t n_q, int64_t k, const int64_t *d_exc_off,
+                       const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out, void *stream);
+int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
+                         const float *d_queries, const float *d_qscale, int64_t n_q, float *d_out, void *stream);
 
 /* Measurement support (the reference has none; examples/bloom_embeddings/performance.py
  * times fit() with time.time()): when enabled, every launch of the engine's kernels is

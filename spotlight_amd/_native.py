@@ -136,6 +136,11 @@ _PROTOTYPES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_shard_topk': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_rows_inv_norm': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'slk_neighbors_topk': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_neighbors_scores': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p]),
     'slk_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'slk_profile_read': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'slk_profile_reset': (C.c_int, [C.c_void_p]),
@@ -576,6 +581,24 @@ class Engine(object):
         candidates by the same order (merge_topk)."""
         self._check(self._lib.slk_shard_topk(self._ctx, C.byref(tables), d_rep, d_rbias, int(n_rows), int(k), d_exc_off,
                                              d_exc_items_local, d_items_local_out, d_scores_out, stream))
+
+    # -- neighbours in the embedding space (include/spotlight_hip.h: slk_neighbors_*) ---------
+    def rows_inv_norm(self, d_table, n_rows, dim, d_out, stream=0):
+        """d_out[n_rows] = 1 / sqrt(sum of squares) of every row of d_table[n_rows][dim] (the d-ordered fma chain); 0 for an
+        all-zero row."""
+        self._check(self._lib.slk_rows_inv_norm(self._ctx, d_table, int(n_rows), int(dim), d_out, stream))
+
+    def neighbors_topk(self, d_table, n_table_rows, dim, d_tscale, d_queries, d_qscale, n_q, k, d_exc_off, d_exc_items,
+                       d_items_out, d_scores_out, stream=0):
+        """The k best rows of d_table per dense query row, by THE ORDER.  Scales both None: dot product; both given (the rows'
+        rows_inv_norm): cosine, (dot * qscale) * tscale.  Exclusions as bilinear_topk takes them, in table rows."""
+        self._check(self._lib.slk_neighbors_topk(self._ctx, d_table, int(n_table_rows), int(dim), d_tscale, d_queries, d_qscale,
+                                                 int(n_q), int(k), d_exc_off, d_exc_items, d_items_out, d_scores_out, stream))
+
+    def neighbors_scores(self, d_table, n_table_rows, dim, d_tscale, d_queries, d_qscale, n_q, d_out, stream=0):
+        """d_out[n_q][n_table_rows]: the score rows neighbors_topk selects from, bit for bit."""
+        self._check(self._lib.slk_neighbors_scores(self._ctx, d_table, int(n_table_rows), int(dim), d_tscale, d_queries, d_qscale,
+                                                   int(n_q), d_out, stream))
 
     # -- measurement -------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -62,6 +62,23 @@ __global__ __launch_bounds__(256) void k_eval_seq_rows(const float *E, slk_bloom
     }
 }
 
+// out[r] = 1 / sqrt(sum_d x[r][d]^2) (slk_rows_inv_norm: the factors of the cosine), the sum formed as THE chain
+// s = fmaf(x_d, x_d, s) over d = 0 .. D-1 from 0 (slk_chain_dot of the row with itself: lane s continues lane s - 1), so that
+// every build and every caller -- a table's own vector, a rank's copy of a fetched row -- defines the same bits.  A row whose
+// sum is exactly 0 gets 0.0f (it scores 0 against everything, never NaN); a NaN or inf sum propagates.
+template <int VEC, int G>
+__global__ __launch_bounds__(256) void k_rows_inv_norm(const float *T, int D, int64_t n, float *out) {
+    constexpr int GPB = 256 / G;
+    const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+    const int d0 = lane * VEC;
+    const bool on = d0 < D;
+    for (int64_t r = (int64_t)blockIdx.x * GPB + grp; r < n; r += (int64_t)gridDim.x * GPB) {
+        const slk_vec<VEC> x = on ? slk_vload<VEC>(T + (size_t)r * D + d0) : slk_vzero<VEC>();
+        const float ss = slk_chain_dot<VEC, G>(x, x);
+        if (lane == 0) out[r] = ss == 0.0f ? 0.0f : 1.0f / sqrtf(ss);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Scores as a GEMM on the matrix cores.  scores[r][i] = <rep_r, V_i> is a (rows x D) x (D x items) product in fp32: the one
 // place on this path where MFMA is the right unit.  v_mfma_f32_32x32x2_f32 is EXACT fp32 -- bit for bit the k-ordered chain
@@ -99,6 +116,8 @@ struct slk_gemm_args {
 };
 
 enum { SLK_GEMM_WRITE = 0, SLK_GEMM_COUNT = 1, SLK_GEMM_SELECT = 2 };  // what the sweep does with a score
+// ... and WRITE / SELECT with the neighbour epilogue (slk_neighbors_*: factors in the place of biases, see k_score_gemm)
+enum { SLK_GEMM_NBR_WRITE = 3, SLK_GEMM_NBR_SELECT = 4 };
 
 #if defined(__HIPCC__)
 typedef float slk_f32x16 __attribute__((ext_vector_type(16)));
@@ -201,11 +220,17 @@ __device__ inline void slk_topk_compact(slk_key *c, unsigned count, int k, int c
     SLK_SUBWAVE_SYNC();
 }
 
+// MODE NBR_WRITE / NBR_SELECT (slk_neighbors_*: rows of any dense table against dense query rows): WRITE / SELECT with no
+// biases; a.rbias / a.bi, where given, are per-row and per-item FACTORS -- the score is (acc * rbias[row]) * bi[item] (cosine:
+// the inverse norms), the bare chain where both are nullptr.  Compile-time variants of the epilogue: the other instantiations
+// are what they were.
 template <int MT, int MODE, bool VEC4, bool AREG>
 __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm_args a) {  // (two workgroups per CU by LDS footprint, eval_gemm: 2 waves per SIMD)
     constexpr int RT = 32 * MT, IB = SLK_GEMM_IB, KC = SLK_GEMM_KC, KS = SLK_GEMM_KS;
     constexpr int BREG = VEC4 ? IB * KC / 256 : 1;  // staged floats per thread (plain tables of dim % 4 == 0)
-    constexpr bool COUNT = MODE == SLK_GEMM_COUNT, SELECT = MODE == SLK_GEMM_SELECT;
+    constexpr bool SCALE = MODE == SLK_GEMM_NBR_WRITE || MODE == SLK_GEMM_NBR_SELECT;
+    constexpr bool COUNT = MODE == SLK_GEMM_COUNT, SELECT = MODE == SLK_GEMM_SELECT || MODE == SLK_GEMM_NBR_SELECT;
+    constexpr bool WRITE = MODE == SLK_GEMM_WRITE || MODE == SLK_GEMM_NBR_WRITE;
     HIP_DYNAMIC_SHARED(float, lds)
     float *sA = lds;                      // [RT][KS]
     float *sB = sA + RT * KS;             // [IB][KS]
@@ -361,9 +386,9 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
         // epilogue: accumulator element v of tile m = (row m*32 + (v&3) + 8*(v>>2) + 4*(lane>>5), item i0 + wave*32 + (lane&31))
         const int64_t item = i0 + wave * 32 + (lane & 31);
         const bool live = item < i_end;
-        const float bias = live ? a.bi[item] : 0.0f;
+        const float bias = SCALE ? ((live && a.bi) ? a.bi[item] : 0.0f) : (live ? a.bi[item] : 0.0f);
         // (WRITE: this lane's output column; the row offsets below are wave-uniform multiples of the row stride)
-        float *ocol = MODE != SLK_GEMM_WRITE ? nullptr : a.out + (size_t)(r0 + 4 * (lane >> 5)) * a.I + item;
+        float *ocol = !WRITE ? nullptr : a.out + (size_t)(r0 + 4 * (lane >> 5)) * a.I + item;
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -374,7 +399,8 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(2) void k_score_gemm(slk_gemm
                 const int row_a = m * 32 + (v & 3) + 8 * (v >> 2);  // lanes 0..31; lanes 32..63 hold row_a + 4
                 const int row = row_a + 4 * (lane >> 5);
                 // k_predict: (dot + bu) + bi;  k_seq_predict: bi + dot
-                const float sc = a.rbias ? (acc[m][v] + s_rb[row]) + bias : bias + acc[m][v];
+                const float sc = SCALE ? (a.bi ? (acc[m][v] * s_rb[row]) * bias : acc[m][v])
+                                       : (a.rbias ? (acc[m][v] + s_rb[row]) + bias : bias + acc[m][v]);
                 if (COUNT) {
                     const float t = s_st[row];
                     cnt[m * 16 + v] += (live && sc > t ? 1u : 0u) + (live && sc == t ? 0x10000u : 0u);
@@ -699,14 +725,15 @@ static gemm_fn gemm_kernel(int mt, bool vec4, bool areg) {
 }
 
 // one sweep of the item table per tile of 32 * mt rows.  `count`: compare with a.st and add into a.gt / a.eq, else store a.out
-static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bool count, hipStream_t s) {
+// `scale`: the neighbour epilogue (tables: a stand-in whose d_param[1] / d_param[3] are the table and its factors or nullptr)
+static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bool count, hipStream_t s, bool scale = false) {
     slk_bloom_to_dev(tables->item_bloom, &a.ib);
     a.V = (const float *)tables->d_param[1];
     a.bi = (const float *)tables->d_param[3];
     a.D = tables->dim;
     a.I = tables->num_items;
     if (a.R <= 0 || a.I <= 0) return SLK_OK;
-    if (!count && a.R <= 8 && a.ib.n_hash == 0 && a.D % 4 == 0) {
+    if (!count && !scale && a.R <= 8 && a.ib.n_hash == 0 && a.D % 4 == 0) {
         // a handful of rows: the streaming form (k_score_rows), two workgroups per CU each sweeping whole blocks of 256 items
         // (option "eval_items_per_wg": the cut given, a test and measurement switch)
         int64_t per = ctx->opt_eval_items_per_wg;
@@ -750,7 +777,9 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
     const size_t half_lds = ctx->lds_per_cu / 2 - 256;
     if (lds < half_lds && half_lds <= ctx->lds_per_block) lds = half_lds;
     const bool areg = vec4 && a.D <= SLK_GEMM_KC;
-    gemm_fn fn = count ? gemm_kernel<SLK_GEMM_COUNT>(mt, vec4, areg) : gemm_kernel<SLK_GEMM_WRITE>(mt, vec4, areg);
+    gemm_fn fn = scale   ? gemm_kernel<SLK_GEMM_NBR_WRITE>(mt, vec4, areg)
+                 : count ? gemm_kernel<SLK_GEMM_COUNT>(mt, vec4, areg)
+                         : gemm_kernel<SLK_GEMM_WRITE>(mt, vec4, areg);
     if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, dim3((unsigned)chunks, (unsigned)row_tiles), dim3(256), lds, s, a);
     SLK_LAUNCH_CHECK(ctx, "k_score_gemm");
@@ -1104,10 +1133,10 @@ static size_t topk_lds(int mt, int cap) {
     return ((size_t)(32 * mt + SLK_GEMM_IB) * SLK_GEMM_KS + 4 * 32 * mt) * 4 + (size_t)32 * mt * ((size_t)cap * 8 + 32);
 }
 
-// rep / rbias / gmap: the rows' representations as eval_gemm takes them (row r = group r); d_exc_off[R + 1]
+// rep / rbias / gmap: the rows' representations as eval_gemm takes them (row r = group r); d_exc_off[R + 1]; `scale` as there
 static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, const float *rep, const float *rbias,
                     const int64_t *gmap, int64_t R, int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items,
-                    int64_t *d_items_out, float *d_scores_out, hipStream_t s) {
+                    int64_t *d_items_out, float *d_scores_out, hipStream_t s, bool scale = false) {
     int rc;
     const int64_t I = tables->num_items;
     const int D = tables->dim;
@@ -1151,7 +1180,7 @@ static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, con
     a.exc_items = d_exc_items;
     const bool vec4 = a.ib.n_hash == 0 && D % 4 == 0;
     const bool areg = vec4 && D <= SLK_GEMM_KC;
-    gemm_fn fn = gemm_kernel<SLK_GEMM_SELECT>(mt, vec4, areg);
+    gemm_fn fn = scale ? gemm_kernel<SLK_GEMM_NBR_SELECT>(mt, vec4, areg) : gemm_kernel<SLK_GEMM_SELECT>(mt, vec4, areg);
     const size_t lds = topk_lds(mt, cap);
     if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int64_t row_step = 16384;
@@ -1256,6 +1285,107 @@ SLK_EXPORT int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float
     slk_prof_begin(ctx, SLK_K_SCORE, s);
     rc = topk_run(ctx, "slk_shard_topk", local, d_rep, d_rbias, nullptr, n_rows, k, d_exc_off, d_exc_items_local, d_items_local_out,
                   d_scores_out, s);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+// ---- neighbours in the embedding space: rows of ANY dense table against dense query rows (the SCALE epilogue) -----------------
+static int check_neighbor_args(slk_ctx *ctx, const char *who, const float *d_table, int64_t n_table_rows, int64_t dim,
+                               const float *d_tscale, const float *d_queries, const float *d_qscale, int64_t n_q, int *vec, int *g) {
+    if (!d_table) return slk_fail(ctx, SLK_EINVAL, "%s: d_table is NULL", who);
+    if (n_table_rows <= 0) return slk_fail(ctx, SLK_EINVAL, "%s: no table rows (n_table_rows = %lld)", who, (long long)n_table_rows);
+    if (n_table_rows >= ((int64_t)1 << 32) - 1)
+        return slk_fail(ctx, SLK_EINVAL, "%s: %lld table rows, ids must fit 32 bits", who, (long long)n_table_rows);
+    if (dim < 1) return slk_fail(ctx, SLK_EINVAL, "%s: dim = %lld, at least 1", who, (long long)dim);
+    if (dim > 256 || !slk_pick_layout((int)dim, vec, g))
+        return slk_fail(ctx, SLK_EINVAL, "%s: embedding dim %lld unsupported (need dim %% 4 == 0 and <= 256, or dim <= 64)", who, (long long)dim);
+    if (n_q < 0 || (n_q > 0 && !d_queries)) return slk_fail(ctx, SLK_EINVAL, "%s: bad arguments (the queries)", who);
+    if ((d_tscale == nullptr) != (d_qscale == nullptr))
+        return slk_fail(ctx, SLK_EINVAL, "%s: d_tscale and d_qscale go together (both: cosine, neither: dot)", who);
+    if (ctx->pp_active && (d_table == ctx->pp_src_u || (d_queries && d_queries == ctx->pp_src_u)))
+        return slk_fail(ctx, SLK_EINVAL, "%s: the user rows of this table are ping-ponged (slk_user_pingpong_begin): the array holds only "
+                                         "some of the current rows until slk_user_pingpong_end", who);
+    return SLK_OK;
+}
+
+// the table as the sweep's item side: rows in slot 1, their factors (or nullptr) where the item biases go
+static void neighbor_tables(slk_tables *t, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale) {
+    memset(t, 0, sizeof(*t));
+    t->d_param[1] = const_cast<float *>(d_table);
+    t->d_param[3] = const_cast<float *>(d_tscale);
+    t->num_items = n_table_rows;
+    t->dim = (int32_t)dim;
+}
+
+SLK_EXPORT int slk_rows_inv_norm(slk_ctx *ctx, const float *d_table, int64_t n_rows, int64_t dim, float *d_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g;
+    if (n_rows < 0) return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: n_rows = %lld", (long long)n_rows);
+    if (dim < 1) return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: dim = %lld, at least 1", (long long)dim);
+    if (dim > 256 || !slk_pick_layout((int)dim, &vec, &g))
+        return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: embedding dim %lld unsupported (need dim %% 4 == 0 and <= 256, or dim <= 64)",
+                        (long long)dim);
+    if (n_rows == 0) return SLK_OK;
+    if (!d_table || !d_out) return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: d_table / d_out is NULL");
+    if (ctx->pp_active && d_table == ctx->pp_src_u)
+        return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: the user rows of this table are ping-ponged (slk_user_pingpong_begin): the "
+                                         "array holds only some of the current rows until slk_user_pingpong_end");
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+#define SLK_ROWS(V_, G_)                                                                                                 \
+    hipLaunchKernelGGL((k_rows_inv_norm<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, d_table, \
+                       (int)dim, n_rows, d_out)
+    SLK_FOR_LAYOUT(vec, g, SLK_ROWS);
+#undef SLK_ROWS
+    SLK_LAUNCH_CHECK(ctx, "k_rows_inv_norm");
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+SLK_EXPORT int slk_neighbors_topk(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
+                                  const float *d_queries, const float *d_qscale, int64_t n_q, int64_t k, const int64_t *d_exc_off,
+                                  const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_topk_args(ctx, "slk_neighbors_topk", n_q, d_queries, k, d_exc_off, d_exc_items, d_items_out, d_scores_out))) return rc;
+    if ((rc = check_neighbor_args(ctx, "slk_neighbors_topk", d_table, n_table_rows, dim, d_tscale, d_queries, d_qscale, n_q, &vec, &g)))
+        return rc;
+    if (n_q == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_tables t;
+    neighbor_tables(&t, d_table, n_table_rows, dim, d_tscale);
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    rc = topk_run(ctx, "slk_neighbors_topk", &t, d_queries, d_qscale, nullptr, n_q, k, d_exc_off, d_exc_items, d_items_out,
+                  d_scores_out, s, true);
+    slk_prof_end(ctx, s);
+    return rc;
+}
+
+SLK_EXPORT int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
+                                    const float *d_queries, const float *d_qscale, int64_t n_q, float *d_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int vec, g, rc;
+    if ((rc = check_neighbor_args(ctx, "slk_neighbors_scores", d_table, n_table_rows, dim, d_tscale, d_queries, d_qscale, n_q, &vec, &g)))
+        return rc;
+    if (n_q > 0 && !d_out) return slk_fail(ctx, SLK_EINVAL, "slk_neighbors_scores: the output (d_out) is NULL");
+    if (n_q == 0) return SLK_OK;
+    SLK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    slk_tables t;
+    neighbor_tables(&t, d_table, n_table_rows, dim, d_tscale);
+    slk_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    a.rep = d_queries;
+    a.rbias = d_qscale;
+    a.R = n_q;
+    a.out = d_out;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    rc = eval_gemm(ctx, &t, a, false, s, true);
     slk_prof_end(ctx, s);
     return rc;
 }

@@ -596,6 +596,63 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         dist.all_gather(all_scores, scores, group=self._group)
         return _rec.merge_topk(torch.cat(all_items, dim=1).cpu().numpy(), torch.cat(all_scores, dim=1).cpu().numpy(), k)
 
+    def similar_items(self, item_ids, k=10, metric='cosine', exclude_self=True, exclude=None):
+        """ImplicitFactorizationModel.similar_items, shard by shard: the query rows come from their owners (the bias column is
+        ignored) and every rank forms their inverse norms itself -- the chain the owner's table entry is formed by, the same
+        bits -- then selects the k best of ITS item rows with its own shard's inverse norms (slk_neighbors_topk); exclusion lists
+        are rebuilt per rank as local rows, the [world][n][k] candidates all-gathered as global ids and merged by the same total
+        order -- the arrays of the one-device model.  Every rank makes the same call and gets the same arrays."""
+        from spotlight_amd import recommend as _rec
+        k, metric = _rec.check_k(k), _rec.check_metric(metric)
+        ids = np.ascontiguousarray(np.asarray(item_ids).reshape(-1), dtype=np.int64)
+        if not ids.size:
+            return _rec.empty_result(k)
+        self._check_item_id_max(ids)
+        _host._reject_negative_ids(ids)
+        self._net.train(False)
+        lists = _rec.neighbor_lists(ids, self._num_items, exclude_self, exclude)
+        world, rank = self._world, self._rank
+        w = self._net.tables()
+        device = w[0].device
+        engine, stream = _host._engine_for(device), _host._stream_for(device)
+        n, I = ids.size, self._num_items
+        queries = self._fetch_rows(1, 3, ids, device)[:, :-1].contiguous()
+        cosine = metric == 'cosine'
+        qscale = _rec.inverse_norms(engine, stream, queries) if cosine else None
+        shard = w[1].detach()
+        local = lambda x: x[x % world == rank] // world
+        local_lists = [local(x) for x in lists] if lists is not None else None
+
+        def select(kk):
+            """This rank's kk best as (global ids, scores), padded with -1 / -inf"""
+            if shard.shape[0] == 0:
+                return (torch.full((n, kk), -1, dtype=torch.int64, device=device),
+                        torch.full((n, kk), float('-inf'), dtype=torch.float32, device=device))
+            tscale = _rec.inverse_norms(engine, stream, shard) if cosine else None
+            if kk <= _rec.TOPK_K_MAX:
+                items, scores = _rec.neighbors_fused(engine, stream, shard, tscale, queries, qscale, kk, local_lists)
+            else:
+                items, scores = [torch.from_numpy(a).to(device) for a in
+                                 _rec.neighbors_generic(engine, stream, shard, tscale, queries, qscale, kk, local_lists)]
+            return torch.where(items >= 0, items * world + rank, items), scores
+
+        kk = min(k, local_rows(I, world, 0)) if k > _rec.TOPK_K_MAX else k  # (a large k: no more than the largest shard holds)
+        items, scores = select(kk)
+        if world > 1:
+            all_items = [torch.empty_like(items) for _ in range(world)]
+            all_scores = [torch.empty_like(scores) for _ in range(world)]
+            dist.all_gather(all_items, items, group=self._group)
+            dist.all_gather(all_scores, scores, group=self._group)
+            items, scores = torch.cat(all_items, dim=1), torch.cat(all_scores, dim=1)
+            return _rec.merge_topk(items.cpu().numpy(), scores.cpu().numpy(), k)
+        if kk == k:
+            return items.cpu().numpy(), scores.cpu().numpy()
+        return _rec.merge_topk(items.cpu().numpy(), scores.cpu().numpy(), k)
+
+    def similar_users(self, user_ids, k=10, metric='cosine', exclude_self=True, exclude=None):
+        raise NotImplementedError('similar_users() of the row-sharded model is not built (INTEGRATION.md 2l): user rows are '
+                                  'sharded as item rows are and it would mirror similar_items()')
+
     def predict(self, user_ids, item_ids=None):
         self._check_input(user_ids, item_ids, allow_items_none=True)
         self._net.train(False)

@@ -71,3 +71,90 @@ def generic_topk(score_rows, keys, num_items, k, lists):
             items[r, :len(o)] = o
             scores[r, :len(o)] = row[o]
     return items, scores
+
+
+# ---- similar_items() / similar_users(): neighbours in the embedding space ------------------------------------------------
+# (include/spotlight_hip.h: slk_rows_inv_norm, slk_neighbors_topk, slk_neighbors_scores.)  The score of query q against
+# table row j is the k-ordered fma chain of the two rows ('dot'), or (chain * 1/|q|) * 1/|j| ('cosine'); order, padding and
+# exclusion lists are recommend()'s.  The fused route selects inside the sweep; the generic route sorts score rows a tile at
+# a time (k > TOPK_K_MAX, and what the tests compare the fused route with).
+METRICS = ('cosine', 'dot')
+
+
+def check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError('metric must be one of {}, got {!r}'.format(METRICS, metric))
+    return metric
+
+
+def neighbor_lists(ids, num_rows, exclude_self=True, exclude=None, always=None):
+    """Per query the sorted, distinct table rows to hide, or None: the caller's lists (`exclude`: one index array per query),
+    the query's own id (`exclude_self`) and the rows hidden from everyone (`always`)."""
+    lists = exclusion_lists(exclude, ids, num_rows)
+    always = np.zeros(0, np.int64) if always is None else np.asarray(always, dtype=np.int64).reshape(-1)
+    if lists is None and not exclude_self and not always.size:
+        return None
+    if lists is None:
+        lists = [np.zeros(0, np.int64)] * len(ids)
+    own = (lambda q: [q]) if exclude_self else (lambda q: [])
+    return [np.unique(np.concatenate([x, always, np.asarray(own(q), dtype=np.int64)])).astype(np.int64) for x, q in zip(lists, ids)]
+
+
+def inverse_norms(engine, stream, rows):
+    """float32 [n] device tensor: 1 / |row| by the engine's chain (0 for an all-zero row); `rows`: contiguous [n, dim]."""
+    import torch
+    out = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    engine.rows_inv_norm(rows.data_ptr(), rows.shape[0], rows.shape[1], out.data_ptr(), stream)
+    return out
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def neighbors_fused(engine, stream, table, tscale, queries, qscale, k, lists):
+    """The k best rows of `table` per row of `queries` (device tensors), selected inside the sweep: device tensors
+    (items int64 [n, k], scores float32 [n, k]).  k <= TOPK_K_MAX."""
+    import torch
+    n, device = queries.shape[0], table.device
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    d_eo, d_ei = [dev(a) for a in csr_of(lists)] if lists is not None else (None, None)
+    items = torch.empty((n, k), dtype=torch.int64, device=device)
+    scores = torch.empty((n, k), dtype=torch.float32, device=device)
+    engine.neighbors_topk(table.data_ptr(), table.shape[0], table.shape[1], _ptr(tscale), queries.data_ptr(), _ptr(qscale), n, k,
+                          _ptr(d_eo), _ptr(d_ei), items.data_ptr(), scores.data_ptr(), stream)
+    return items, scores
+
+
+def neighbors_generic(engine, stream, table, tscale, queries, qscale, k, lists):
+    """The same result from score rows (slk_neighbors_scores), a tile of queries at a time, ordered on the host."""
+    import torch
+    n, num_rows = queries.shape[0], table.shape[0]
+
+    def score_rows(idx):
+        lo, m = int(idx[0]), len(idx)
+        out = torch.empty((m, num_rows), dtype=torch.float32, device=table.device)
+        engine.neighbors_scores(table.data_ptr(), num_rows, table.shape[1], _ptr(tscale), queries[lo:lo + m].data_ptr(),
+                                _ptr(qscale[lo:lo + m]) if qscale is not None else None, m, out.data_ptr(), stream)
+        return out.cpu().numpy()
+    return generic_topk(score_rows, np.arange(n), num_rows, k, lists)
+
+
+def similar_rows(engine, stream, table, ids, k, metric, lists, generic=False):
+    """similar_items() / similar_users() over one dense table (a float32 [n, dim] device tensor): the queries are rows `ids` of
+    the table itself, gathered on the device; under 'cosine' the table's inverse norms are computed once and the queries'
+    factors are entries of that vector.  Host arrays (items, scores)."""
+    import torch
+    table = table.detach()
+    if not table.is_contiguous() or table.dtype != torch.float32:
+        raise RuntimeError('the embedding table must be a contiguous fp32 tensor')
+    d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(table.device)
+    queries = table.index_select(0, d_ids)
+    tscale = qscale = None
+    if metric == 'cosine':
+        tscale = inverse_norms(engine, stream, table)
+        qscale = tscale.index_select(0, d_ids)
+    if generic or k > TOPK_K_MAX:
+        return neighbors_generic(engine, stream, table, tscale, queries, qscale, k, lists)
+    items, scores = neighbors_fused(engine, stream, table, tscale, queries, qscale, k, lists)
+    return items.cpu().numpy(), scores.cpu().numpy()

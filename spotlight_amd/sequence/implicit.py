@@ -377,6 +377,18 @@ class ImplicitSequenceModel(object):
                                                scores.data_ptr(), _host._stream_for(device))
         return items.cpu().numpy(), scores.cpu().numpy()
 
+    def similar_items(self, item_ids, k=10, metric='cosine', exclude_self=True, exclude=None):
+        """ImplicitFactorizationModel.similar_items over the network's item embedding table (every representation of this
+        package keeps one: `item_embeddings`).  The padding item (id 0) is never returned, on any row."""
+        return _host.ImplicitFactorizationModel._similar(self, 'item_embeddings', self._num_items, item_ids, k, metric,
+                                                         exclude_self, exclude, always=[PADDING_IDX])
+
+    _embedding_table = _host.ImplicitFactorizationModel._embedding_table
+
+    def _check_item_id_max(self, item_ids):
+        if item_ids.max() >= self._num_items:
+            raise ValueError('Maximum item id greater than number of items in model.')
+
     def _batch_scores(self, sequences):
         """[n_sequences, num_items] device tensor: row r == predict(sequences[r]) (bit-identical), a tile
         of sequences per pass over the item table (csrc/slk_eval.hip); used by evaluation.sequence_mrr_score."""
