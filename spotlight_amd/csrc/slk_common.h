@@ -88,6 +88,41 @@ struct slk_rng_dev {
 
 #define SLK_EXTRA_BUFS 56
 
+// THE table of ctx->extra slots, grouped by owner.  A slot is scratch of its owner's API calls; two names share a number only
+// where written as an alias below, and then at most one of the two owners keeps contents from one API call to a later one.
+enum slk_extra_slot {
+    // slk_shard.hip (SH_UIT / SH_GPOS: adaptive hinge -- the packed 1 + n item lists and global positions, kept from
+    // slk_shard_chunk_begin_adaptive until the chunk's passes)
+    SH_OKEY0 = 0, SH_OKEY1, SH_OVAL0, SH_OVAL1, SH_VSLOT, SH_HIST, SH_SEGSTART, SH_UNITBASE, SH_MBOFF, SH_RID, SH_SEGTAB, SH_GSLOT,
+    SH_UIT = 48, SH_GPOS,
+    // slk_bilinear.hip, the training call (nothing survives it: the user-partial metas, which keep launch stamps across calls,
+    // have a buffer of their own, ctx->upart_meta)
+    BL_UREC = 16, BL_LIVE, BL_LK0, BL_LK1, BL_LV0, BL_LV1, BL_GSN, BL_UPART, BL_LATE_SORT = 38,
+    // slk_seqprep.hip: TS_T0..TS_SORT are temporaries of one call (slk_compact_heads, which slk_embed.hip calls too, uses TS_T3,
+    // TS_T4 and TS_SMALL); TS_USERS..TS_ROWOFF hold the plan from slk_to_sequence_plan until slk_to_sequence_fill
+    TS_T0 = 26, TS_T1, TS_T2, TS_T3, TS_T4, TS_SMALL, TS_SORT, TS_USERS, TS_ITEMS, TS_HEADS, TS_ROWOFF,
+    // slk_shuffle.hip, one slk_shuffle_perm call
+    FY_B0 = TS_T0, FY_B1, FY_B2, FY_B3, FY_B4, FY_SMALL, FY_SORT,  // safe: temporaries of one call on either side
+    // slk_seq.hip, the training call and slk_poolnet_predict (nothing survives either)
+    SQ_MCOUNT = 12, SQ_REP, SQ_BIK0, SQ_BIK1,
+    SQ_BIP0 = BL_UREC, SQ_BIP1,  // safe: no code names SQ_BIK0..SQ_BIP1 (the bloom occurrence lists moved into slk_prep_bufs)
+    SQ_GSN = BL_UPART,           // safe: either side fills and reads it inside one training call
+    SQ_MCOUNT_B = TS_T4,         // safe: the second prep set's mask counts, written and read inside one training call
+    // slk_embed.hip: EM_KEY0..EM_HEADS hold the plan from slk_embedding_backward_plan until slk_embedding_backward_fill
+    EM_SORT = TS_SORT,  // safe: the radix sort's scratch, dead when the sort returns
+    EM_KEY0 = 40, EM_KEY1, EM_PAY0, EM_PAY1, EM_HEADS, EM_PART0, EM_PART1,
+    // slk_epoch.hip, the persistent route of one training call
+    // safe: only slk_embed.hip keeps these four, from a backward's plan to its fill, and the package issues those two back to
+    // back inside one autograd node (spotlight_amd/embedding.py): no training call can run between them
+    EP_COEF = EM_KEY0, EP_BAR, EP_PARTIAL, EP_TOUCH,
+    // slk_eval.hip: the rows' representations, the fused ranking's target scores and counters, the top-k candidates and the
+    // offsets check's flag.  Nothing survives a call, but EV_TOPK / EV_TOPK_FLAG have numbers of their own, not SH_UIT / SH_GPOS:
+    // slk_shard_topk may run on a sharded trainer's ctx between a chunk's begin and its passes
+    EV_REP = 24, EV_RBIAS, EV_ST = 37, EV_CNT = 39, EV_TOPK = 50, EV_TOPK_FLAG,
+    SLK_EXTRA_END  // (the slots above are the highest in use)
+};
+static_assert(SLK_EXTRA_END <= SLK_EXTRA_BUFS, "slk_ctx::extra holds every slot of slk_extra_slot");
+
 // buffers filled by the value-independent prep of one chunk of minibatches (slk_bilinear.hip)
 struct slk_prep_bufs {
     slk_buf neg32, ukey[2], uval[2], uit, ikey[2], ipay[2];
@@ -212,7 +247,7 @@ struct slk_ctx {
     bool sampled_valid = false;         //   false after slk_rng_set_state / a shuffle (whose end only the stream sync knows)
     hipStream_t copy_stream = nullptr;  // small state copies (slk_rng_{set,get}_state): never the null stream
     hipEvent_t ev_start = nullptr, ev_prep[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    slk_buf extra[SLK_EXTRA_BUFS];  // path-specific scratch (slk_shard.hip, slk_seq.hip)
+    slk_buf extra[SLK_EXTRA_BUFS];  // path-specific scratch, indexed by slk_extra_slot
     // row-sharded path (slk_shard.hip): geometry of the chunk staged by slk_shard_chunk_begin/commit
     int64_t shard_n = -1;           // interactions of the committed chunk (-1: none)
     int64_t sh_n = 0;
@@ -290,6 +325,27 @@ hipStream_t slk_copy_stream(slk_ctx *ctx);
         if (e_ != hipSuccess)                                                                \
             return slk_fail((ctx), SLK_EIO, "launch of %s failed: %s", (what), hipGetErrorString(e_)); \
     } while (0)
+
+// The scope of one API call, opened after its argument checks: begin() makes the ctx's device current, notes the stream and
+// opens a profile span of class `cls`; the destructor closes the span on EVERY way out of the scope, the error returns of
+// SLK_HIP / SLK_LAUNCH_CHECK included (a failed call's span is closed and counts as a call).
+struct slk_call {
+    slk_ctx *const ctx;
+    const hipStream_t s;
+    bool open = false;
+    slk_call(slk_ctx *c, void *stream) : ctx(c), s((hipStream_t)stream) {}
+    slk_call(const slk_call &) = delete;
+    int begin(int cls) {
+        SLK_HIP(ctx, hipSetDevice(ctx->device));
+        ctx->last_stream = s;
+        slk_prof_begin(ctx, cls, s);
+        open = true;
+        return SLK_OK;
+    }
+    ~slk_call() {
+        if (open) slk_prof_end(ctx, s);
+    }
+};
 
 // MT19937 jump-ahead geometry: stream w of a draw (one wavefront of k_mt_stream, started by workgroup w - 1 of k_mt_jump)
 // produces state blocks [w*SLK_MT_JUMP_BLOCKS, (w+1)*SLK_MT_JUMP_BLOCKS); one group of launches covers up to

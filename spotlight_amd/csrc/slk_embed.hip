@@ -12,8 +12,6 @@
 #include "slk_common.h"
 #include "slk_kernels.h"
 
-enum { EM_SORT = 32, EM_KEY0 = 40, EM_KEY1, EM_PAY0, EM_PAY1, EM_HEADS, EM_PART0, EM_PART1 };  // ctx->extra slots
-
 static int em_threads_per_row(int D, int VEC) {
     int need = (D + VEC - 1) / VEC, t = 1;
     while (t < need && t < 64) t <<= 1;

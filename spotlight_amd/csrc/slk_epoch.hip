@@ -804,8 +804,6 @@ bool slk_epoch_eligible(const slk_ctx *ctx, const slk_tables *tables, const slk_
     return true;
 }
 
-enum { EP_COEF = 40, EP_BAR, EP_PARTIAL, EP_TOUCH };  // ctx->extra slots
-
 static int epoch_upd_of(const slk_optim *optim) {
     switch (optim->kind) {
         case SLK_OPT_ADAGRAD: return SLK_EUPD_ADAGRAD;

@@ -18,8 +18,6 @@
 
 #include "slk_kernels.h"
 
-enum { EV_REP = 24, EV_RBIAS };  // ctx->extra slots
-
 // representation of row r for BilinearNet: the user's embedding vector and bias
 template <int VEC, int G>
 __global__ __launch_bounds__(256) void k_eval_user_rows(const float *U, const float *bu, slk_bloom_dev ub, int D,
@@ -712,33 +710,93 @@ __global__ __launch_bounds__(256) void k_topk_check_offsets(const int64_t *exc_o
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-enum { EV_ST = 37, EV_CNT = 39, EV_TOPK = 48, EV_TOPK_FLAG = 49 };  // ctx->extra slots of the fused ranking (24, 25: the representations)
-
 typedef void (*gemm_fn)(slk_gemm_args);
 
-// areg: the representations' operand in registers for the whole sweep (plain tables of dim <= 64)
-template <int COUNT>  // (the sweep's MODE)
-static gemm_fn gemm_kernel(int mt, bool vec4, bool areg) {
-    if (areg) return mt == 1 ? k_score_gemm<1, COUNT, true, true> : k_score_gemm<2, COUNT, true, true>;
-    if (mt == 1) return vec4 ? k_score_gemm<1, COUNT, true, false> : k_score_gemm<1, COUNT, false, false>;
-    return vec4 ? k_score_gemm<2, COUNT, true, false> : k_score_gemm<2, COUNT, false, false>;
+// the rows' representations: group g's is row gmap[g] (nullptr: g) of rep / rbias (rbias nullptr: no row bias, PoolNet)
+struct eval_rows {
+    const float *rep, *rbias;
+    const int64_t *gmap;
+};
+
+// the groups' exclusion lists: group g's excluded items are items[off[g] .. off[g + 1]) (off nullptr: none)
+struct eval_exc {
+    const int64_t *off, *items;
+};
+
+// the swept table: an slk_tables' item side, or any dense table with its rows' factors (or nullptr) where the item biases go
+// (the neighbour entries)
+struct eval_table {
+    const float *V, *bi;
+    const slk_bloom *bloom;
+    int D;
+    int64_t I;
+};
+
+static eval_table item_table(const slk_tables *t) {
+    return {(const float *)t->d_param[1], (const float *)t->d_param[3], t->item_bloom, t->dim, t->num_items};
 }
 
-// one sweep of the item table per tile of 32 * mt rows.  `count`: compare with a.st and add into a.gt / a.eq, else store a.out
-// `scale`: the neighbour epilogue (tables: a stand-in whose d_param[1] / d_param[3] are the table and its factors or nullptr)
-static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bool count, hipStream_t s, bool scale = false) {
-    slk_bloom_to_dev(tables->item_bloom, &a.ib);
-    a.V = (const float *)tables->d_param[1];
-    a.bi = (const float *)tables->d_param[3];
-    a.D = tables->dim;
-    a.I = tables->num_items;
+// the sweep's arguments for R rows (row r = group r) against the table; what the MODE reads or writes is the caller's to add
+static slk_gemm_args sweep_args(const eval_table &t, const eval_rows &rows, int64_t R) {
+    slk_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    a.rep = rows.rep;
+    a.rbias = rows.rbias;
+    a.gmap = rows.gmap;
+    a.R = R;
+    slk_bloom_to_dev(t.bloom, &a.ib);
+    a.V = t.V;
+    a.bi = t.bi;
+    a.D = t.D;
+    a.I = t.I;
+    return a;
+}
+
+// areg: the representations' operand in registers for the whole sweep (plain tables of dim <= 64)
+template <int MODE>
+static gemm_fn gemm_kernel(int mt, bool vec4, bool areg) {
+    if (areg) return mt == 1 ? k_score_gemm<1, MODE, true, true> : k_score_gemm<2, MODE, true, true>;
+    if (mt == 1) return vec4 ? k_score_gemm<1, MODE, true, false> : k_score_gemm<1, MODE, false, false>;
+    return vec4 ? k_score_gemm<2, MODE, true, false> : k_score_gemm<2, MODE, false, false>;
+}
+
+// k_score_gemm for a MODE (SLK_GEMM_*), a tile of 32 * mt rows and the table of `a`, granted `lds` bytes of LDS
+static int gemm_kernel_for(slk_ctx *ctx, int mode, const slk_gemm_args &a, int mt, size_t lds, gemm_fn *fn) {
+    const bool vec4 = a.ib.n_hash == 0 && a.D % 4 == 0;
+    const bool areg = vec4 && a.D <= SLK_GEMM_KC;
+    switch (mode) {
+        case SLK_GEMM_WRITE: *fn = gemm_kernel<SLK_GEMM_WRITE>(mt, vec4, areg); break;
+        case SLK_GEMM_COUNT: *fn = gemm_kernel<SLK_GEMM_COUNT>(mt, vec4, areg); break;
+        case SLK_GEMM_SELECT: *fn = gemm_kernel<SLK_GEMM_SELECT>(mt, vec4, areg); break;
+        case SLK_GEMM_NBR_WRITE: *fn = gemm_kernel<SLK_GEMM_NBR_WRITE>(mt, vec4, areg); break;
+        default: *fn = gemm_kernel<SLK_GEMM_NBR_SELECT>(mt, vec4, areg); break;
+    }
+    if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return SLK_OK;
+}
+
+// LDS of k_score_gemm without the SELECT modes' candidates: the row tile, one staged block, the tile's biases and targets
+static size_t gemm_lds(int mt) { return ((size_t)(32 * mt + SLK_GEMM_IB) * SLK_GEMM_KS + 4 * 32 * mt) * 4; }
+
+// items per workgroup of a sweep of I items for `rows` rows in tiles of `rt`: the option's value (0: the automatic cut), else
+// enough workgroups for the chip (~4 per CU over all row tiles; 2 per CU for a single row tile, whose workgroups are all
+// resident at once: longer sweeps amortise a workgroup's first, unhidden block); whole blocks of `block` items
+static int64_t sweep_cut(int64_t I, int64_t rows, int rt, int64_t opt, int num_cus, int block) {
+    const int64_t row_tiles = (rows + rt - 1) / rt;
+    int64_t want = ((row_tiles == 1 ? 2 : 4) * (int64_t)num_cus + row_tiles - 1) / row_tiles;
+    if (want < 1) want = 1;
+    const int64_t per = opt > 0 ? opt : (I + want - 1) / want;
+    return (per + block - 1) / block * block;
+}
+
+// one sweep of the table per tile of 32 * mt rows in MODE WRITE / NBR_WRITE (store a.out) or COUNT (compare with a.st and add
+// into a.gt / a.eq); `a` from sweep_args.  (The SELECT modes tile their rows themselves: topk_run.)
+static int eval_gemm(slk_ctx *ctx, int mode, slk_gemm_args a, hipStream_t s) {
     if (a.R <= 0 || a.I <= 0) return SLK_OK;
-    if (!count && !scale && a.R <= 8 && a.ib.n_hash == 0 && a.D % 4 == 0) {
+    if (mode == SLK_GEMM_WRITE && a.R <= 8 && a.ib.n_hash == 0 && a.D % 4 == 0) {
         // a handful of rows: the streaming form (k_score_rows), two workgroups per CU each sweeping whole blocks of 256 items
         // (option "eval_items_per_wg": the cut given, a test and measurement switch)
-        int64_t per = ctx->opt_eval_items_per_wg;
-        if (per <= 0) per = (a.I + 2 * (int64_t)ctx->num_cus - 1) / (2 * (int64_t)ctx->num_cus);
-        per = (per + SLK_ROWS_IB - 1) / SLK_ROWS_IB * SLK_ROWS_IB;
+        const int64_t per = sweep_cut(a.I, a.R, 8, ctx->opt_eval_items_per_wg, ctx->num_cus, SLK_ROWS_IB);
         a.items_per_wg = per;
         const int nr = a.R == 1 ? 1 : (a.R == 2 ? 2 : (a.R <= 4 ? 4 : 8));
         const size_t lds = ((size_t)SLK_ROWS_IB * SLK_GEMM_KS + (size_t)nr * SLK_GEMM_KC + nr) * 4;
@@ -753,21 +811,13 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
     // blocks the CU has in flight), 32 for a handful (predict: one row -- a 32-row tile keeps the matrix-core time below the
     // table's streaming time)
     const int mt = a.R > 32 ? 2 : 1;
-    const bool vec4 = a.ib.n_hash == 0 && a.D % 4 == 0;
     const int64_t row_tiles = (a.R + 32 * mt - 1) / (32 * mt);
-    // item chunks: enough workgroups for the chip (~4 per CU over all row tiles; 2 per CU for a single row tile, whose
-    // workgroups are all resident at once: longer sweeps amortise a workgroup's first, unhidden block), whole blocks of
-    // SLK_GEMM_IB items
-    int64_t want = ((row_tiles == 1 ? 2 : 4) * (int64_t)ctx->num_cus + row_tiles - 1) / row_tiles;
-    if (want < 1) want = 1;
-    int64_t per = ctx->opt_eval_items_per_wg;  // (0: the automatic cut)
-    if (per <= 0) per = (a.I + want - 1) / want;
-    per = (per + SLK_GEMM_IB - 1) / SLK_GEMM_IB * SLK_GEMM_IB;
+    int64_t per = sweep_cut(a.I, a.R, 32 * mt, ctx->opt_eval_items_per_wg, ctx->num_cus, SLK_GEMM_IB);
     if (per > ((int64_t)1 << 22)) per = (int64_t)1 << 22;  // (the packed per-lane counters hold 2^16 - 1 columns: 2^23 items)
     a.items_per_wg = per;
     const int64_t chunks = (a.I + per - 1) / per;
     if (row_tiles > 65535) return slk_fail(ctx, SLK_EINVAL, "scoring: %lld rows per call, at most %d", (long long)a.R, 65535 * 32 * mt);
-    size_t lds = ((size_t)(32 * mt + SLK_GEMM_IB) * SLK_GEMM_KS + 4 * 32 * mt) * 4;
+    size_t lds = gemm_lds(mt);
     // two resident workgroups per CU, by LDS footprint: the registers would allow three, and three share the LDS bandwidth and
     // the L2 worse (4096 x 10^6: 8.3 ms against 7.06, profiles/r04_h_bench_eval_{2,3}wg.json)
     // (the pad is half of the CU's LDS as the DEVICE reports it -- 160 KB on gfx950 -- and is skipped where a workgroup cannot be
@@ -776,34 +826,35 @@ static int eval_gemm(slk_ctx *ctx, const slk_tables *tables, slk_gemm_args a, bo
         return slk_fail(ctx, SLK_EINVAL, "scoring: the sweep needs %zu B of LDS per workgroup, the device grants %zu", lds, ctx->lds_per_block);
     const size_t half_lds = ctx->lds_per_cu / 2 - 256;
     if (lds < half_lds && half_lds <= ctx->lds_per_block) lds = half_lds;
-    const bool areg = vec4 && a.D <= SLK_GEMM_KC;
-    gemm_fn fn = scale   ? gemm_kernel<SLK_GEMM_NBR_WRITE>(mt, vec4, areg)
-                 : count ? gemm_kernel<SLK_GEMM_COUNT>(mt, vec4, areg)
-                         : gemm_kernel<SLK_GEMM_WRITE>(mt, vec4, areg);
-    if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc;
+    gemm_fn fn;
+    if ((rc = gemm_kernel_for(ctx, mode, a, mt, lds, &fn))) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)chunks, (unsigned)row_tiles), dim3(256), lds, s, a);
     SLK_LAUNCH_CHECK(ctx, "k_score_gemm");
     return SLK_OK;
 }
 
-// The rows' representations.  Plain user table: the table itself, addressed through the ids (*rowmap = d_users; no kernel, no
-// copy).  BloomEmbedding user table: the hashed rows are summed into scratch first (*rowmap = NULL).
+// out[r][i]: R rows against every row of the table (MODE WRITE, or NBR_WRITE with the neighbour epilogue)
+static int eval_scores(slk_ctx *ctx, int mode, const eval_table &t, const eval_rows &rows, int64_t R, float *d_out, hipStream_t s) {
+    slk_gemm_args a = sweep_args(t, rows, R);
+    a.out = d_out;
+    return eval_gemm(ctx, mode, a, s);
+}
+
+// The rows' representations.  Plain user table: the table itself, addressed through the ids (gmap = d_users; no kernel, no
+// copy).  BloomEmbedding user table: the hashed rows are summed into scratch first (gmap = NULL).
 static int eval_user_rows(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const int64_t *d_users, int64_t n_users,
-                          const float **rep, const float **rbias, const int64_t **rowmap, hipStream_t s) {
+                          eval_rows *rows, hipStream_t s) {
     int rc;
     if (!tables->user_bloom || tables->user_bloom->n_hash == 0) {
-        *rep = (const float *)tables->d_param[0];
-        *rbias = (const float *)tables->d_param[2];
-        *rowmap = d_users;
+        *rows = {(const float *)tables->d_param[0], (const float *)tables->d_param[2], d_users};
         return SLK_OK;
     }
-    *rowmap = nullptr;
     const int D = tables->dim;
     if ((rc = slk_ensure(ctx, ctx->extra[EV_REP], (size_t)n_users * D * 4))) return rc;
     if ((rc = slk_ensure(ctx, ctx->extra[EV_RBIAS], (size_t)n_users * 4))) return rc;
     float *rep_w = (float *)ctx->extra[EV_REP].p, *rbias_w = (float *)ctx->extra[EV_RBIAS].p;
-    *rep = rep_w;
-    *rbias = rbias_w;
+    *rows = {rep_w, rbias_w, nullptr};
     slk_bloom_dev ubd;
     slk_bloom_to_dev(tables->user_bloom, &ubd);
 #define SLK_ROWS(V_, G_)                                                                                          \
@@ -817,16 +868,17 @@ static int eval_user_rows(slk_ctx *ctx, const slk_tables *tables, int vec, int g
 }
 
 static int eval_seq_rows(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const int64_t *d_sequences, int64_t n_seq,
-                         int64_t seq_len, float **rep, hipStream_t s) {
+                         int64_t seq_len, eval_rows *rows, hipStream_t s) {
     int rc;
     const int D = tables->dim;
     if ((rc = slk_ensure(ctx, ctx->extra[EV_REP], (size_t)n_seq * D * 4))) return rc;
-    *rep = (float *)ctx->extra[EV_REP].p;
+    float *rep_w = (float *)ctx->extra[EV_REP].p;
+    *rows = {rep_w, nullptr, nullptr};
     slk_bloom_dev ibd;
     slk_bloom_to_dev(tables->item_bloom, &ibd);
 #define SLK_ROWS(V_, G_)                                                                                         \
     hipLaunchKernelGGL((k_eval_seq_rows<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_seq, 256 / G_)), dim3(256), 0, s, \
-                       (const float *)tables->d_param[1], ibd, D, d_sequences, n_seq, (int)seq_len, *rep)
+                       (const float *)tables->d_param[1], ibd, D, d_sequences, n_seq, (int)seq_len, rep_w)
     SLK_FOR_LAYOUT(vec, g, SLK_ROWS);
 #undef SLK_ROWS
     SLK_LAUNCH_CHECK(ctx, "k_eval_seq_rows");
@@ -840,23 +892,11 @@ SLK_EXPORT int slk_bilinear_scores(slk_ctx *ctx, const slk_tables *tables, const
     if ((rc = slk_check_tables(ctx, tables, 15u, &vec, &g))) return rc;
     if (n_users < 0 || (n_users > 0 && (!d_users || !d_out))) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_scores: bad arguments");
     if (n_users == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    const float *rep, *rbias;
-    const int64_t *gmap;
-    if ((rc = eval_user_rows(ctx, tables, vec, g, d_users, n_users, &rep, &rbias, &gmap, s))) return rc;
-    a.rep = rep;
-    a.rbias = rbias;
-    a.gmap = gmap;
-    a.R = n_users;
-    a.out = d_out;
-    rc = eval_gemm(ctx, tables, a, false, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_user_rows(ctx, tables, vec, g, d_users, n_users, &rows, call.s))) return rc;
+    return eval_scores(ctx, SLK_GEMM_WRITE, item_table(tables), rows, n_users, d_out, call.s);
 }
 
 SLK_EXPORT int slk_poolnet_scores(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_sequences, int64_t n_seq,
@@ -867,25 +907,16 @@ SLK_EXPORT int slk_poolnet_scores(slk_ctx *ctx, const slk_tables *tables, const 
     if (n_seq < 0 || seq_len < 1 || (n_seq > 0 && (!d_sequences || !d_out)))
         return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_scores: bad arguments");
     if (n_seq == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    float *rep;
-    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_sequences, n_seq, seq_len, &rep, s))) return rc;
-    a.rep = rep;
-    a.R = n_seq;
-    a.out = d_out;
-    rc = eval_gemm(ctx, tables, a, false, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_sequences, n_seq, seq_len, &rows, call.s))) return rc;
+    return eval_scores(ctx, SLK_GEMM_WRITE, item_table(tables), rows, n_seq, d_out, call.s);
 }
 
 // Fused ranking: rank_out[r] = rankdata(-scores(group row_group[r]) with the group's exclusions pushed last)[row_target[r]]
 // without a score matrix, in three stages: the target scores (vector unit), ONE counting sweep of the item table per 64 rows
-// (matrix cores) with the exclusion lists' corrections (vector unit), and the counts' way out.  rep / rbias: the groups'
+// (matrix cores) with the exclusion lists' corrections (vector unit), and the counts' way out.  rows: the groups'
 // representations.  The one-device entries run the stages back to back (rank_fused); the sharded entries run the first two on
 // ONE RANK's item rows with a collective of the host's after each (slk_shard_target_scores / slk_shard_rank_counts).
 struct rank_counters {
@@ -909,24 +940,20 @@ static int rank_scratch(slk_ctx *ctx, int64_t n_rows, bool want_st, float **st, 
 
 // stage 1: st[r] = the score of row r's target (-FLT_MAX where the target is on its group's exclusion list; `shard`: -INFINITY
 // where d_row_target[r] is no row of these tables)
-static int rank_target_scores(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
-                              const int64_t *gmap, const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows,
-                              const int64_t *d_exc_off, const int64_t *d_exc_items, bool shard, float *st, hipStream_t s) {
-    slk_bloom_dev ibd;
-    slk_bloom_to_dev(tables->item_bloom, &ibd);
-    const float *V = (const float *)tables->d_param[1], *bi = (const float *)tables->d_param[3];
-    const int D = tables->dim;
-    const int64_t I = tables->num_items;
+static int rank_target_scores(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const eval_rows &rows,
+                              const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows, const eval_exc &exc,
+                              bool shard, float *st, hipStream_t s) {
+    const slk_gemm_args a = sweep_args(item_table(tables), rows, n_rows);
 #define SLK_TGT(V_, G_)                                                                                                      \
     do {                                                                                                                     \
         if (shard)                                                                                                           \
             hipLaunchKernelGGL((k_rank_target_scores<V_, G_, true>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)),      \
-                               dim3(256), 0, s, rep, rbias, d_row_group, gmap, V, bi, ibd, D, I, d_row_target, d_exc_off,    \
-                               d_exc_items, n_rows, st);                                                                     \
+                               dim3(256), 0, s, a.rep, a.rbias, d_row_group, a.gmap, a.V, a.bi, a.ib, a.D, a.I, d_row_target, \
+                               exc.off, exc.items, n_rows, st);                                                              \
         else                                                                                                                 \
             hipLaunchKernelGGL((k_rank_target_scores<V_, G_, false>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)),     \
-                               dim3(256), 0, s, rep, rbias, d_row_group, gmap, V, bi, ibd, D, I, d_row_target, d_exc_off,    \
-                               d_exc_items, n_rows, st);                                                                     \
+                               dim3(256), 0, s, a.rep, a.rbias, d_row_group, a.gmap, a.V, a.bi, a.ib, a.D, a.I, d_row_target, \
+                               exc.off, exc.items, n_rows, st);                                                              \
     } while (0)
     SLK_FOR_LAYOUT(vec, g, SLK_TGT);
 #undef SLK_TGT
@@ -934,32 +961,22 @@ static int rank_target_scores(slk_ctx *ctx, const slk_tables *tables, int vec, i
     return SLK_OK;
 }
 
-// stage 2: c.gt / c.eq = #{items of these tables scoring > / == st[r]}; c.dgt / c.deq (written iff d_exc_off): what pushing the
+// stage 2: c.gt / c.eq = #{items of these tables scoring > / == st[r]}; c.dgt / c.deq (written iff exc.off): what pushing the
 // exclusion list's items of these tables to -FLT_MAX changes of them
-static int rank_counts(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
-                       const int64_t *gmap, const int64_t *d_row_group, int64_t n_rows, const int64_t *d_exc_off,
-                       const int64_t *d_exc_items, const float *st, const rank_counters &c, hipStream_t s) {
+static int rank_counts(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const eval_rows &rows, const int64_t *d_row_group,
+                       int64_t n_rows, const eval_exc &exc, const float *st, const rank_counters &c, hipStream_t s) {
     int rc;
     SLK_HIP(ctx, hipMemsetAsync(c.gt, 0, (size_t)n_rows * 8, s));
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.rep = rep;
-    a.rbias = rbias;
+    slk_gemm_args a = sweep_args(item_table(tables), rows, n_rows);
     a.rowmap = d_row_group;
-    a.gmap = gmap;
-    a.R = n_rows;
     a.st = st;
     a.gt = c.gt;
     a.eq = c.eq;
-    if ((rc = eval_gemm(ctx, tables, a, true, s))) return rc;
-    if (d_exc_off) {
-        slk_bloom_dev ibd;
-        slk_bloom_to_dev(tables->item_bloom, &ibd);
-        const float *V = (const float *)tables->d_param[1], *bi = (const float *)tables->d_param[3];
-        const int D = tables->dim;
+    if ((rc = eval_gemm(ctx, SLK_GEMM_COUNT, a, s))) return rc;
+    if (exc.off) {
 #define SLK_EXC(V_, G_)                                                                                             \
-    hipLaunchKernelGGL((k_rank_exclusions<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, rep,   \
-                       rbias, d_row_group, gmap, V, bi, ibd, D, d_exc_off, d_exc_items, st, n_rows, c.dgt, c.deq)
+    hipLaunchKernelGGL((k_rank_exclusions<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, a.rep, \
+                       a.rbias, d_row_group, a.gmap, a.V, a.bi, a.ib, a.D, exc.off, exc.items, st, n_rows, c.dgt, c.deq)
         SLK_FOR_LAYOUT(vec, g, SLK_EXC);
 #undef SLK_EXC
         SLK_LAUNCH_CHECK(ctx, "k_rank_exclusions");
@@ -967,29 +984,25 @@ static int rank_counts(slk_ctx *ctx, const slk_tables *tables, int vec, int g, c
     return SLK_OK;
 }
 
-static int rank_fused(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const float *rep, const float *rbias,
-                      const int64_t *gmap, const int64_t *d_row_group, const int64_t *d_row_target, int64_t n_rows, const int64_t *d_exc_off,
-                      const int64_t *d_exc_items, double *d_rank_out, hipStream_t s) {
+static int rank_fused(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const eval_rows &rows, const int64_t *d_row_group,
+                      const int64_t *d_row_target, int64_t n_rows, const eval_exc &exc, double *d_rank_out, hipStream_t s) {
     int rc;
     float *st = nullptr;
     rank_counters c;
     if ((rc = rank_scratch(ctx, n_rows, true, &st, &c))) return rc;
-    if ((rc = rank_target_scores(ctx, tables, vec, g, rep, rbias, gmap, d_row_group, d_row_target, n_rows, d_exc_off, d_exc_items,
-                                 false, st, s)))
-        return rc;
-    if ((rc = rank_counts(ctx, tables, vec, g, rep, rbias, gmap, d_row_group, n_rows, d_exc_off, d_exc_items, st, c, s))) return rc;
+    if ((rc = rank_target_scores(ctx, tables, vec, g, rows, d_row_group, d_row_target, n_rows, exc, false, st, s))) return rc;
+    if ((rc = rank_counts(ctx, tables, vec, g, rows, d_row_group, n_rows, exc, st, c, s))) return rc;
     hipLaunchKernelGGL(k_rank_final, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)c.gt,
-                       (const unsigned *)c.eq, d_exc_off ? (const int *)c.dgt : (const int *)nullptr,
-                       d_exc_off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_rank_out);
+                       (const unsigned *)c.eq, exc.off ? (const int *)c.dgt : (const int *)nullptr,
+                       exc.off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_rank_out);
     SLK_LAUNCH_CHECK(ctx, "k_rank_final");
     return SLK_OK;
 }
 
+// (exc.off without exc.items is NOT refused here: an empty torch tensor's data_ptr() is 0, so all-empty lists arrive that way)
 static int check_rank_args(slk_ctx *ctx, const char *who, int64_t n_groups, const void *groups, const int64_t *d_row_group,
-                           const int64_t *d_row_target, int64_t n_rows, const int64_t *d_exc_off, const int64_t *d_exc_items,
-                           const double *d_rank_out) {
-    if (n_groups < 0 || n_rows < 0 || (n_groups > 0 && !groups) || (n_rows > 0 && (!d_row_group || !d_row_target || !d_rank_out)) ||
-        (d_exc_off && !d_exc_items && n_groups > 0 && false))
+                           const int64_t *d_row_target, int64_t n_rows, const double *d_rank_out) {
+    if (n_groups < 0 || n_rows < 0 || (n_groups > 0 && !groups) || (n_rows > 0 && (!d_row_group || !d_row_target || !d_rank_out)))
         return slk_fail(ctx, SLK_EINVAL, "%s: bad arguments", who);
     if (n_rows > 0 && n_groups == 0) return slk_fail(ctx, SLK_EINVAL, "%s: rows without groups", who);
     return SLK_OK;
@@ -1001,20 +1014,13 @@ SLK_EXPORT int slk_bilinear_rank(slk_ctx *ctx, const slk_tables *tables, const i
     if (!ctx) return SLK_EINVAL;
     int vec, g, rc;
     if ((rc = slk_check_tables(ctx, tables, 15u, &vec, &g))) return rc;
-    if ((rc = check_rank_args(ctx, "slk_bilinear_rank", n_groups, d_group_users, d_row_group, d_row_target, n_rows, d_exc_off,
-                              d_exc_items, d_rank_out)))
-        return rc;
+    if ((rc = check_rank_args(ctx, "slk_bilinear_rank", n_groups, d_group_users, d_row_group, d_row_target, n_rows, d_rank_out))) return rc;
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    const float *rep, *rbias;
-    const int64_t *gmap;
-    if ((rc = eval_user_rows(ctx, tables, vec, g, d_group_users, n_groups, &rep, &rbias, &gmap, s))) return rc;
-    rc = rank_fused(ctx, tables, vec, g, rep, rbias, gmap, d_row_group, d_row_target, n_rows, d_exc_off, d_exc_items, d_rank_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_user_rows(ctx, tables, vec, g, d_group_users, n_groups, &rows, call.s))) return rc;
+    return rank_fused(ctx, tables, vec, g, rows, d_row_group, d_row_target, n_rows, {d_exc_off, d_exc_items}, d_rank_out, call.s);
 }
 
 SLK_EXPORT int slk_poolnet_rank(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_group_sequences, int64_t n_groups,
@@ -1024,19 +1030,14 @@ SLK_EXPORT int slk_poolnet_rank(slk_ctx *ctx, const slk_tables *tables, const in
     int vec, g, rc;
     if ((rc = slk_check_tables(ctx, tables, 10u, &vec, &g))) return rc;
     if (seq_len < 1) return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_rank: seq_len %lld", (long long)seq_len);
-    if ((rc = check_rank_args(ctx, "slk_poolnet_rank", n_groups, d_group_sequences, d_row_group, d_row_target, n_rows, d_exc_off,
-                              d_exc_items, d_rank_out)))
+    if ((rc = check_rank_args(ctx, "slk_poolnet_rank", n_groups, d_group_sequences, d_row_group, d_row_target, n_rows, d_rank_out)))
         return rc;
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    float *rep;
-    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_group_sequences, n_groups, seq_len, &rep, s))) return rc;
-    rc = rank_fused(ctx, tables, vec, g, rep, nullptr, nullptr, d_row_group, d_row_target, n_rows, d_exc_off, d_exc_items, d_rank_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_group_sequences, n_groups, seq_len, &rows, call.s))) return rc;
+    return rank_fused(ctx, tables, vec, g, rows, d_row_group, d_row_target, n_rows, {d_exc_off, d_exc_items}, d_rank_out, call.s);
 }
 
 // ---- sharded evaluation: one rank's item rows against caller-supplied representations ----------------------------------------
@@ -1064,14 +1065,10 @@ SLK_EXPORT int slk_shard_target_scores(slk_ctx *ctx, const slk_tables *local, co
         return slk_fail(ctx, SLK_EINVAL, "slk_shard_target_scores: bad arguments");
     if (n_rows > 0 && n_groups == 0) return slk_fail(ctx, SLK_EINVAL, "slk_shard_target_scores: rows without groups");
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    rc = rank_target_scores(ctx, local, vec, g, d_rep, d_rbias, nullptr, d_row_group, d_row_target_local, n_rows, d_exc_off,
-                            d_exc_items_local, true, d_st_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    return rank_target_scores(ctx, local, vec, g, {d_rep, d_rbias, nullptr}, d_row_group, d_row_target_local, n_rows,
+                              {d_exc_off, d_exc_items_local}, true, d_st_out, call.s);
 }
 
 SLK_EXPORT int slk_shard_rank_counts(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias,
@@ -1085,22 +1082,18 @@ SLK_EXPORT int slk_shard_rank_counts(slk_ctx *ctx, const slk_tables *local, cons
         return slk_fail(ctx, SLK_EINVAL, "slk_shard_rank_counts: bad arguments");
     if (n_rows > 0 && n_groups == 0) return slk_fail(ctx, SLK_EINVAL, "slk_shard_rank_counts: rows without groups");
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    hipStream_t s = call.s;
     rank_counters c;
     if ((rc = rank_scratch(ctx, n_rows, false, nullptr, &c))) return rc;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    rc = rank_counts(ctx, local, vec, g, d_rep, d_rbias, nullptr, d_row_group, n_rows, d_exc_off, d_exc_items_local, d_st, c, s);
-    if (rc == SLK_OK) {
-        hipLaunchKernelGGL(k_rank_counts_out, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)c.gt,
-                           (const unsigned *)c.eq, d_exc_off ? (const int *)c.dgt : (const int *)nullptr,
-                           d_exc_off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_gt_out, d_eq_out);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = slk_fail(ctx, SLK_EIO, "launch of %s failed: %s", "k_rank_counts_out", hipGetErrorString(e));
-    }
-    slk_prof_end(ctx, s);
-    return rc;
+    if ((rc = rank_counts(ctx, local, vec, g, {d_rep, d_rbias, nullptr}, d_row_group, n_rows, {d_exc_off, d_exc_items_local}, d_st, c, s)))
+        return rc;
+    hipLaunchKernelGGL(k_rank_counts_out, dim3(slk_grid_for(ctx, (size_t)n_rows, 256)), dim3(256), 0, s, (const unsigned *)c.gt,
+                       (const unsigned *)c.eq, d_exc_off ? (const int *)c.dgt : (const int *)nullptr,
+                       d_exc_off ? (const int *)c.deq : (const int *)nullptr, n_rows, d_gt_out, d_eq_out);
+    SLK_LAUNCH_CHECK(ctx, "k_rank_counts_out");
+    return SLK_OK;
 }
 
 SLK_EXPORT int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
@@ -1110,44 +1103,29 @@ SLK_EXPORT int slk_shard_scores(slk_ctx *ctx, const slk_tables *local, const flo
     if ((rc = check_shard_eval(ctx, "slk_shard_scores", local, d_rep, d_rbias, n_rows, &vec, &g))) return rc;
     if (n_rows > 0 && !d_out) return slk_fail(ctx, SLK_EINVAL, "slk_shard_scores: bad arguments");
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.rep = d_rep;
-    a.rbias = d_rbias;
-    a.R = n_rows;
-    a.out = d_out;
-    rc = eval_gemm(ctx, local, a, false, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    return eval_scores(ctx, SLK_GEMM_WRITE, item_table(local), {d_rep, d_rbias, nullptr}, n_rows, d_out, call.s);
 }
-
 
 // ---- top-k: MODE SELECT of the sweep + k_topk_merge ------------------------------------------------------------------------------
 #define SLK_TOPK_SCRATCH_BYTES ((size_t)64 << 20)  // candidate scratch of one launch (rows are processed in tiles to stay below it)
 
-static size_t topk_lds(int mt, int cap) {
-    return ((size_t)(32 * mt + SLK_GEMM_IB) * SLK_GEMM_KS + 4 * 32 * mt) * 4 + (size_t)32 * mt * ((size_t)cap * 8 + 32);
-}
+static size_t topk_lds(int mt, int cap) { return gemm_lds(mt) + (size_t)32 * mt * ((size_t)cap * 8 + 32); }
 
-// rep / rbias / gmap: the rows' representations as eval_gemm takes them (row r = group r); d_exc_off[R + 1]; `scale` as there
-static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, const float *rep, const float *rbias,
-                    const int64_t *gmap, int64_t R, int64_t k, const int64_t *d_exc_off, const int64_t *d_exc_items,
-                    int64_t *d_items_out, float *d_scores_out, hipStream_t s, bool scale = false) {
+// the top k of R rows (row r = group r, exc.off[R + 1]) against the table; mode: SLK_GEMM_SELECT or SLK_GEMM_NBR_SELECT
+static int topk_run(slk_ctx *ctx, const char *who, int mode, const eval_table &t, const eval_rows &rows, int64_t R, int64_t k,
+                    const eval_exc &exc, int64_t *d_items_out, float *d_scores_out, hipStream_t s) {
     int rc;
-    const int64_t I = tables->num_items;
-    const int D = tables->dim;
+    const int64_t I = t.I;
     if (I <= 0) return slk_fail(ctx, SLK_EINVAL, "%s: no items", who);
     if (I >= ((int64_t)1 << 32) - 1) return slk_fail(ctx, SLK_EINVAL, "%s: %lld items, ids must fit 32 bits", who, (long long)I);
-    if (d_exc_off) {
-        // the offsets index d_exc_items inside the sweep: checked here, the one host wait of the call
+    if (exc.off) {
+        // the offsets index exc.items inside the sweep: checked here, the one host wait of the call
         if ((rc = slk_ensure(ctx, ctx->extra[EV_TOPK_FLAG], sizeof(int)))) return rc;
         int *d_bad = (int *)ctx->extra[EV_TOPK_FLAG].p, h_bad = 0;
         SLK_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_topk_check_offsets, dim3(slk_grid_for(ctx, (size_t)R, 256)), dim3(256), 0, s, d_exc_off, R, d_bad);
+        hipLaunchKernelGGL(k_topk_check_offsets, dim3(slk_grid_for(ctx, (size_t)R, 256)), dim3(256), 0, s, exc.off, R, d_bad);
         SLK_LAUNCH_CHECK(ctx, "k_topk_check_offsets");
         SLK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
         SLK_HIP(ctx, hipStreamSynchronize(s));
@@ -1168,32 +1146,18 @@ static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, con
     }
     if (!mt) return slk_fail(ctx, SLK_EINVAL, "%s: k = %lld does not fit the device's %zu B of LDS per workgroup", who, (long long)k, ctx->lds_per_block);
     const int RT = 32 * mt;
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    slk_bloom_to_dev(tables->item_bloom, &a.ib);
-    a.V = (const float *)tables->d_param[1];
-    a.bi = (const float *)tables->d_param[3];
-    a.D = D;
-    a.I = I;
+    slk_gemm_args a = sweep_args(t, rows, R);
     a.k = (int)k;
     a.cap = cap;
-    a.exc_items = d_exc_items;
-    const bool vec4 = a.ib.n_hash == 0 && D % 4 == 0;
-    const bool areg = vec4 && D <= SLK_GEMM_KC;
-    gemm_fn fn = scale ? gemm_kernel<SLK_GEMM_NBR_SELECT>(mt, vec4, areg) : gemm_kernel<SLK_GEMM_SELECT>(mt, vec4, areg);
+    a.exc_items = exc.items;
     const size_t lds = topk_lds(mt, cap);
-    if (lds > 48 * 1024) SLK_HIP(ctx, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    gemm_fn fn;
+    if ((rc = gemm_kernel_for(ctx, mode, a, mt, lds, &fn))) return rc;
     int64_t row_step = 16384;
     for (int64_t r_lo = 0; r_lo < R; r_lo += row_step) {
         int64_t n = R - r_lo < row_step ? R - r_lo : row_step;
         // item chunks: the option's, else as eval_gemm cuts them (~4 workgroups per CU over all row tiles)
-        int64_t per = ctx->opt_topk_items_per_wg;
-        if (per <= 0) {
-            const int64_t row_tiles = (n + RT - 1) / RT;
-            int64_t want = ((row_tiles == 1 ? 2 : 4) * (int64_t)ctx->num_cus + row_tiles - 1) / row_tiles;
-            per = (I + want - 1) / want;
-        }
-        per = (per + SLK_GEMM_IB - 1) / SLK_GEMM_IB * SLK_GEMM_IB;
+        const int64_t per = sweep_cut(I, n, RT, ctx->opt_topk_items_per_wg, ctx->num_cus, SLK_GEMM_IB);
         const int64_t chunks = (I + per - 1) / per;
         if (chunks > 0x7fffffff) return slk_fail(ctx, SLK_EINVAL, "%s: %lld item chunks per row tile", who, (long long)chunks);
         // rows of this launch: as many whole tiles as keep the candidate scratch bounded
@@ -1208,10 +1172,10 @@ static int topk_run(slk_ctx *ctx, const char *who, const slk_tables *tables, con
         a.cand = (slk_key *)ctx->extra[EV_TOPK].p;
         a.items_per_wg = per;
         a.R = n;
-        a.rep = gmap ? rep : rep + (size_t)r_lo * D;
-        a.rbias = (gmap || !rbias) ? rbias : rbias + r_lo;
-        a.gmap = gmap ? gmap + r_lo : nullptr;
-        a.exc_off = d_exc_off ? d_exc_off + r_lo : nullptr;
+        a.rep = rows.gmap ? rows.rep : rows.rep + (size_t)r_lo * t.D;
+        a.rbias = (rows.gmap || !rows.rbias) ? rows.rbias : rows.rbias + r_lo;
+        a.gmap = rows.gmap ? rows.gmap + r_lo : nullptr;
+        a.exc_off = exc.off ? exc.off + r_lo : nullptr;
         hipLaunchKernelGGL(fn, dim3((unsigned)chunks, (unsigned)((n + RT - 1) / RT)), dim3(256), lds, s, a);
         SLK_LAUNCH_CHECK(ctx, "k_score_gemm<SELECT>");
         hipLaunchKernelGGL(k_topk_merge, dim3(slk_grid_for(ctx, (size_t)n, 4)), dim3(256), 0, s, (const slk_key *)a.cand, n,
@@ -1238,16 +1202,12 @@ SLK_EXPORT int slk_bilinear_topk(slk_ctx *ctx, const slk_tables *tables, const i
     if ((rc = slk_check_tables(ctx, tables, 15u, &vec, &g))) return rc;
     if ((rc = check_topk_args(ctx, "slk_bilinear_topk", n_users, d_users, k, d_exc_off, d_exc_items, d_items_out, d_scores_out))) return rc;
     if (n_users == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    const float *rep, *rbias;
-    const int64_t *gmap;
-    if ((rc = eval_user_rows(ctx, tables, vec, g, d_users, n_users, &rep, &rbias, &gmap, s))) return rc;
-    rc = topk_run(ctx, "slk_bilinear_topk", tables, rep, rbias, gmap, n_users, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_user_rows(ctx, tables, vec, g, d_users, n_users, &rows, call.s))) return rc;
+    return topk_run(ctx, "slk_bilinear_topk", SLK_GEMM_SELECT, item_table(tables), rows, n_users, k, {d_exc_off, d_exc_items},
+                    d_items_out, d_scores_out, call.s);
 }
 
 SLK_EXPORT int slk_poolnet_topk(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_sequences, int64_t n_seq, int64_t seq_len,
@@ -1259,15 +1219,12 @@ SLK_EXPORT int slk_poolnet_topk(slk_ctx *ctx, const slk_tables *tables, const in
     if (seq_len < 1) return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_topk: seq_len %lld", (long long)seq_len);
     if ((rc = check_topk_args(ctx, "slk_poolnet_topk", n_seq, d_sequences, k, d_exc_off, d_exc_items, d_items_out, d_scores_out))) return rc;
     if (n_seq == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    float *rep;
-    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_sequences, n_seq, seq_len, &rep, s))) return rc;
-    rc = topk_run(ctx, "slk_poolnet_topk", tables, rep, nullptr, nullptr, n_seq, k, d_exc_off, d_exc_items, d_items_out, d_scores_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    eval_rows rows;
+    if ((rc = eval_seq_rows(ctx, tables, vec, g, d_sequences, n_seq, seq_len, &rows, call.s))) return rc;
+    return topk_run(ctx, "slk_poolnet_topk", SLK_GEMM_SELECT, item_table(tables), rows, n_seq, k, {d_exc_off, d_exc_items},
+                    d_items_out, d_scores_out, call.s);
 }
 
 SLK_EXPORT int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float *d_rep, const float *d_rbias, int64_t n_rows,
@@ -1279,14 +1236,10 @@ SLK_EXPORT int slk_shard_topk(slk_ctx *ctx, const slk_tables *local, const float
     if ((rc = check_topk_args(ctx, "slk_shard_topk", n_rows, d_rep, k, d_exc_off, d_exc_items_local, d_items_local_out, d_scores_out)))
         return rc;
     if (n_rows == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    rc = topk_run(ctx, "slk_shard_topk", local, d_rep, d_rbias, nullptr, n_rows, k, d_exc_off, d_exc_items_local, d_items_local_out,
-                  d_scores_out, s);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    return topk_run(ctx, "slk_shard_topk", SLK_GEMM_SELECT, item_table(local), {d_rep, d_rbias, nullptr}, n_rows, k,
+                    {d_exc_off, d_exc_items_local}, d_items_local_out, d_scores_out, call.s);
 }
 
 // ---- neighbours in the embedding space: rows of ANY dense table against dense query rows (the SCALE epilogue) -----------------
@@ -1308,18 +1261,9 @@ static int check_neighbor_args(slk_ctx *ctx, const char *who, const float *d_tab
     return SLK_OK;
 }
 
-// the table as the sweep's item side: rows in slot 1, their factors (or nullptr) where the item biases go
-static void neighbor_tables(slk_tables *t, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale) {
-    memset(t, 0, sizeof(*t));
-    t->d_param[1] = const_cast<float *>(d_table);
-    t->d_param[3] = const_cast<float *>(d_tscale);
-    t->num_items = n_table_rows;
-    t->dim = (int32_t)dim;
-}
-
 SLK_EXPORT int slk_rows_inv_norm(slk_ctx *ctx, const float *d_table, int64_t n_rows, int64_t dim, float *d_out, void *stream) {
     if (!ctx) return SLK_EINVAL;
-    int vec, g;
+    int vec, g, rc;
     if (n_rows < 0) return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: n_rows = %lld", (long long)n_rows);
     if (dim < 1) return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: dim = %lld, at least 1", (long long)dim);
     if (dim > 256 || !slk_pick_layout((int)dim, &vec, &g))
@@ -1330,17 +1274,14 @@ SLK_EXPORT int slk_rows_inv_norm(slk_ctx *ctx, const float *d_table, int64_t n_r
     if (ctx->pp_active && d_table == ctx->pp_src_u)
         return slk_fail(ctx, SLK_EINVAL, "slk_rows_inv_norm: the user rows of this table are ping-ponged (slk_user_pingpong_begin): the "
                                          "array holds only some of the current rows until slk_user_pingpong_end");
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
 #define SLK_ROWS(V_, G_)                                                                                                 \
-    hipLaunchKernelGGL((k_rows_inv_norm<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, s, d_table, \
+    hipLaunchKernelGGL((k_rows_inv_norm<V_, G_>), dim3(slk_grid_for(ctx, (size_t)n_rows, 256 / G_)), dim3(256), 0, call.s, d_table, \
                        (int)dim, n_rows, d_out)
     SLK_FOR_LAYOUT(vec, g, SLK_ROWS);
 #undef SLK_ROWS
     SLK_LAUNCH_CHECK(ctx, "k_rows_inv_norm");
-    slk_prof_end(ctx, s);
     return SLK_OK;
 }
 
@@ -1353,16 +1294,10 @@ SLK_EXPORT int slk_neighbors_topk(slk_ctx *ctx, const float *d_table, int64_t n_
     if ((rc = check_neighbor_args(ctx, "slk_neighbors_topk", d_table, n_table_rows, dim, d_tscale, d_queries, d_qscale, n_q, &vec, &g)))
         return rc;
     if (n_q == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_tables t;
-    neighbor_tables(&t, d_table, n_table_rows, dim, d_tscale);
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    rc = topk_run(ctx, "slk_neighbors_topk", &t, d_queries, d_qscale, nullptr, n_q, k, d_exc_off, d_exc_items, d_items_out,
-                  d_scores_out, s, true);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    return topk_run(ctx, "slk_neighbors_topk", SLK_GEMM_NBR_SELECT, {d_table, d_tscale, nullptr, (int)dim, n_table_rows},
+                    {d_queries, d_qscale, nullptr}, n_q, k, {d_exc_off, d_exc_items}, d_items_out, d_scores_out, call.s);
 }
 
 SLK_EXPORT int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
@@ -1373,40 +1308,27 @@ SLK_EXPORT int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t 
         return rc;
     if (n_q > 0 && !d_out) return slk_fail(ctx, SLK_EINVAL, "slk_neighbors_scores: the output (d_out) is NULL");
     if (n_q == 0) return SLK_OK;
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_tables t;
-    neighbor_tables(&t, d_table, n_table_rows, dim, d_tscale);
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.rep = d_queries;
-    a.rbias = d_qscale;
-    a.R = n_q;
-    a.out = d_out;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
-    rc = eval_gemm(ctx, &t, a, false, s, true);
-    slk_prof_end(ctx, s);
-    return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
+    return eval_scores(ctx, SLK_GEMM_NBR_WRITE, {d_table, d_tscale, nullptr, (int)dim, n_table_rows}, {d_queries, d_qscale, nullptr},
+                       n_q, d_out, call.s);
 }
 
 // predict() of ONE representation against EVERY item (slk_bilinear_predict / slk_poolnet_predict with d_items == NULL):
-// the same sweep with a 32-row tile holding one live row
+// the same sweep with a 32-row tile holding one live row.  (Inside the caller's profile span: no scope of its own.)
 int slk_eval_predict_all(slk_ctx *ctx, const slk_tables *tables, const float *rep, const float *rbias, const int64_t *gmap,
                          float *d_out, hipStream_t s) {
-    slk_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    a.rep = rep;
-    a.rbias = rbias;
-    a.gmap = gmap;
-    a.R = 1;
-    a.out = d_out;
-    return eval_gemm(ctx, tables, a, false, s);
+    return eval_scores(ctx, SLK_GEMM_WRITE, item_table(tables), {rep, rbias, gmap}, 1, d_out, s);
 }
 
 int slk_eval_user_rep(slk_ctx *ctx, const slk_tables *tables, int vec, int g, const int64_t *d_user, const float **rep,
                       const float **rbias, const int64_t **gmap, hipStream_t s) {
-    return eval_user_rows(ctx, tables, vec, g, d_user, 1, rep, rbias, gmap, s);
+    eval_rows rows = {nullptr, nullptr, nullptr};
+    const int rc = eval_user_rows(ctx, tables, vec, g, d_user, 1, &rows, s);
+    *rep = rows.rep;
+    *rbias = rows.rbias;
+    *gmap = rows.gmap;
+    return rc;
 }
 
 SLK_EXPORT int slk_rank_targets(slk_ctx *ctx, float *d_scores, int64_t n_rows, int64_t num_items,
@@ -1417,20 +1339,18 @@ SLK_EXPORT int slk_rank_targets(slk_ctx *ctx, float *d_scores, int64_t n_rows, i
     if (n_rows < 0 || num_items < 1 || n_exc < 0 || n_tgt < 0 || (n_rows > 0 && !d_scores) ||
         (n_exc > 0 && (!d_exc_rows || !d_exc_items)) || (n_tgt > 0 && (!d_tgt_rows || !d_tgt_items || !d_rank_out)))
         return slk_fail(ctx, SLK_EINVAL, "slk_rank_targets: bad arguments");
-    SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
-    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    int rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SCORE))) return rc;
     if (n_exc > 0) {
-        hipLaunchKernelGGL(k_eval_exclude, dim3(slk_grid_for(ctx, (size_t)n_exc, 256)), dim3(256), 0, s, d_scores,
+        hipLaunchKernelGGL(k_eval_exclude, dim3(slk_grid_for(ctx, (size_t)n_exc, 256)), dim3(256), 0, call.s, d_scores,
                            num_items, d_exc_rows, d_exc_items, n_exc);
         SLK_LAUNCH_CHECK(ctx, "k_eval_exclude");
     }
     if (n_tgt > 0) {
-        hipLaunchKernelGGL(k_eval_rank, dim3(slk_grid_for(ctx, (size_t)n_tgt, 1, 32)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_eval_rank, dim3(slk_grid_for(ctx, (size_t)n_tgt, 1, 32)), dim3(256), 0, call.s,
                            (const float *)d_scores, num_items, d_tgt_rows, d_tgt_items, n_tgt, d_rank_out);
         SLK_LAUNCH_CHECK(ctx, "k_eval_rank");
     }
-    slk_prof_end(ctx, s);
     return SLK_OK;
 }

@@ -15,9 +15,8 @@
 // of users present, number of rows).
 #include "slk_common.h"
 
-enum { TS_T0 = 26, TS_T1, TS_T2, TS_T3, TS_T4, TS_SMALL, TS_SORT, TS_USERS = 33, TS_ITEMS, TS_HEADS, TS_ROWOFF };
-// ctx->extra slots: 26..32 are temporaries shared with slk_shuffle.hip (nothing survives a call);
-// 33..36 hold the plan (sorted users, sorted items, segment heads, row offsets) until slk_to_sequence_fill.
+// ctx->extra slots (slk_common.h): TS_T0..TS_SORT are temporaries (nothing survives a call); TS_USERS..TS_ROWOFF hold the plan
+// (sorted users, sorted items, segment heads, row offsets) until slk_to_sequence_fill.
 
 #define TS_TILE 2048  // elements per workgroup of the scan kernels (256 threads x 8)
 

@@ -41,10 +41,6 @@
 #define SLK_MAX_WORLD 64
 #define SLK_SHARD_MAX_BINS 2048  // world * units per chunk
 
-// scratch slots in ctx->extra
-enum { SH_OKEY0 = 0, SH_OKEY1, SH_OVAL0, SH_OVAL1, SH_VSLOT, SH_HIST, SH_SEGSTART, SH_UNITBASE, SH_MBOFF, SH_RID,
-       SH_SEGTAB, SH_GSLOT, SH_UIT = 48, SH_GPOS = 49 };  // (48, 49: adaptive hinge -- the packed 1 + n item lists, global positions)
-
 static inline int64_t pad_slots(int64_t lookups) { return (lookups + SLK_SHARD_BLOCK - 1) / SLK_SHARD_BLOCK * SLK_SHARD_BLOCK; }
 
 SLK_EXPORT int64_t slk_shard_buffer_floats(int32_t dim, int64_t slots) { return pad_slots(slots) * (int64_t)(dim + 1); }

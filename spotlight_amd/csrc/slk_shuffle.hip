@@ -40,8 +40,6 @@
 #define FY_TILE 2048       // words per workgroup in the scan kernels (256 threads x 8)
 #define FY_TAIL 4096       // draws for i < FY_TAIL are taken by one wavefront (k_fy_tail)
 
-enum { FY_B0 = 26, FY_B1, FY_B2, FY_B3, FY_B4, FY_SMALL, FY_SORT };  // ctx->extra slots (32 in all)
-
 __device__ __forceinline__ uint32_t fy_temper(uint32_t y) {
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680u;

@@ -82,3 +82,7 @@ def test_shards_merge_to_the_one_device_result(be, D, I, n_rows, k, W):
 
 def test_refusals(be):
     tc.check_refusals(be)
+
+
+def test_profile_survives_a_refusal(be):
+    tc.check_profile_survives_refusal(be)

@@ -340,6 +340,36 @@ def check_shards(be, D, I, n_rows, k, W):
         assert_same((merged_i, merged_s), whole, ('shards', D, I, n_rows, k, W, exc is None))
 
 
+def check_profile_survives_refusal(be):
+    """A call refused AFTER its profile span has opened (decreasing offsets: the check runs on the device) closes the span: the
+    profile stays readable, the refused call counts as a call, and the class's time is a time (at most the wall time around
+    the two calls; an end event that was never recorded gives an error on HIP and a meaningless difference on the emulator)."""
+    import time
+    rng = np.random.RandomState(89)
+    U, I, D, k = 3, 8, 4, 2
+    dev = be.model(random_params(rng, U, I, D))
+    users = np.arange(U, dtype=np.int64)
+    d_users = be.alloc(users)
+    d_eo, d_ei = be.alloc(np.array([0, 2, 1, 3], dtype=np.int64)), be.alloc(np.arange(3, dtype=np.int64))
+    d_items, d_scores = be.alloc(np.zeros((U, k), dtype=np.int64)), be.alloc(np.zeros((U, k), dtype=np.float32))
+    be.engine.profile_reset()
+    be.engine.profile_enable(True)
+    t0 = time.perf_counter()
+    try:
+        with pytest.raises(_native.SlkError, match='not sorted'):
+            be.engine.bilinear_topk(dev.tables, be.ptr(d_users), U, k, be.ptr(d_eo), be.ptr(d_ei), be.ptr(d_items), be.ptr(d_scores),
+                                    be.stream)
+        got = bilinear_topk(be, dev, users, k)  # (reads the results back: the stream is synchronised)
+    finally:
+        be.engine.profile_enable(False)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    calls, ms = be.engine.profile_read()['score']
+    print('score class: %d calls, %.6f ms of %.3f ms wall' % (calls, ms, wall_ms))
+    assert calls == 2
+    assert 0 <= ms <= wall_ms
+    assert_same(got, host_topk(bilinear_scores(be, dev, users), None, k), 'after a refusal under the profile')
+
+
 def check_refusals(be):
     rng = np.random.RandomState(83)
     U, I, D, n, k = 30, 20, 8, 4, 5
