@@ -202,7 +202,11 @@ const char *slk_last_error(const slk_ctx *ctx); /* ctx may be NULL: last create 
  *                         workgroup of the writing / counting sweep covers (rounded up to whole blocks: 128 items, 256 in the
  *                         streaming form that serves up to 8 rows of a plain table with dim % 4 == 0; never more than 2^22, which
  *                         the packed rank counters can hold; 0, the default: cut from the device's CU count).  A test and measurement
- *                         switch: every score and every rank is the same under every value.  slk_*_topk keeps its own option */
+ *                         switch: every score and every rank is the same under every value.  slk_*_topk keeps its own option
+ *   "foldin_wg_min_len"   slk_bilinear_foldin: histories of at least this many interactions take the workgroup route (one
+ *                         256-thread workgroup per user), shorter ones the wave route (one wavefront per user); 0, the default:
+ *                         the measured crossover.  A test and measurement switch, and like "adaptive_late_min_batch" NOT
+ *                         bit-neutral: the two routes add a user's gradient terms in different (each fixed) orders */
 int slk_ctx_set_option(slk_ctx *ctx, const char *name, int64_t value);
 /* The current value of an option (ABI 9): lets a caller change an option for one piece of work and restore it afterwards --
  * a ctx is shared by every model of a process on its device (spotlight_amd/_native.py: `with engine.options(...)`). */
@@ -674,6 +678,44 @@ int slk_neighbors_topk(slk_ctx *ctx, const float *d_table, int64_t n_table_rows,
                        const int64_t *d_exc_items, int64_t *d_items_out, float *d_scores_out, void *stream);
 int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_rows, int64_t dim, const float *d_tscale,
                          const float *d_queries, const float *d_qscale, int64_t n_q, float *d_out, void *stream);
+
+/* Fold-in (added to ABI 14: one new entry, nothing existing changes, SLK_ABI_VERSION stays): rows for users who arrived after
+ * fit(), learned from their own histories against FROZEN item tables.  The reference has no such call; ONE fold-in step of user u
+ * is one reference minibatch (spotlight/factorization/implicit.py:229-243) made of u's interactions alone, restricted to tables
+ * 0 and 2.
+ *   tables   d_param[0] = [n_new_users, dim] and d_param[2] = [n_new_users]: the NEW users' rows and biases, the caller's, initialised
+ *            by the caller (num_users == n_new_users); d_param[1] / d_param[3]: the model's item tables, READ-ONLY here --
+ *            byte-identical after the call, as is everything in optimizer-state slots 1 and 3, which are never read or written.
+ *   optim    kind and hyper-parameters of the step; d_state1[0] / [2] (and d_state2[0] / [2] for the Adam kinds) belong to the new
+ *            rows.  ADAGRAD, SGD, SPARSE_ADAM, ADAM_DENSE (with weight decay), ADAGRAD_DENSE (weight decay, lr_decay).  The row is
+ *            touched at every step, so the sparse and dense forms differ only by weight decay, lr_decay and the two Adam
+ *            roundings.  optim->step is advanced by n_steps on return.
+ *   d_off[n_new_users + 1] / d_items[n]   the histories, CSR; duplicates kept, order within a user = order of appearance
+ *   d_neg[n_steps][nn][n]                 negatives, nn = n_neg for adaptive hinge, else 1: block t is what
+ *                                         sample_items(num_items, (nn, n)) returns (nn == 1: sample_items(num_items, n))
+ *   d_loss   NULL or [n_steps][n_new_users]: the loss of user u's minibatch at step t
+ * For every user u with m = d_off[u + 1] - d_off[u] > 0 and every step t = 0 .. n_steps - 1, in order:
+ *   1. score(u, i) = (dot(row_u, item_row_i) + bias_u) + item_bias_i (BilinearNet, as the training passes form it);
+ *   2. the loss is the reference's loss function over THIS USER's m interactions as one minibatch (inv_b = 1 / m): positives
+ *      d_items[d_off[u] .. d_off[u + 1]), negatives d_neg[t][:, d_off[u] .. d_off[u + 1]).  Adaptive hinge: per interaction the
+ *      candidate with the largest score, the first on ties, and the hinge against it -- the reference's view(n, B) of a
+ *      one-user minibatch;
+ *   3. the gradient with respect to row_u and bias_u only;
+ *   4. one optimizer step on row_u and bias_u, step number optim->step + t + 1; the per-step coefficients are formed on the host
+ *      in double and rounded to float, as the training path forms them per minibatch.
+ *   5. m == 0: row, bias and state untouched, the user's loss slots 0.0f.
+ * A user's result depends on their own history, their negatives and the route their history's length selects
+ * ("foldin_wg_min_len") -- not on the grid and not on who else is in the call.  Hence, bit for bit:
+ *   batch composition   folding users {A, B, C} in one call == folding each alone with their slice of the negatives, == any
+ *                       permutation of the users;
+ *   step composition    one call with n_steps = T == T calls with n_steps = 1, the state carried in the caller's arrays.
+ * Ids are NOT range-checked (as in slk_bilinear_train; spotlight_amd checks them on the host).  Refused with SLK_EINVAL: a NULL
+ * required pointer, n_steps < 1, n_new_users < 1, n < 0, an explicit-feedback loss, n_neg < 1 under adaptive hinge, a dim without
+ * a row layout, a bloom table on either side, item biases inside an open bias-shadow scope.  Nothing is retained, nothing is
+ * allocated (no scratch at all), no host wait; profiled under SLK_K_USER_PASS. */
+int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_off, const int64_t *d_items,
+                        int64_t n_new_users, int64_t n, int32_t loss, int32_t n_neg, int64_t n_steps, const int64_t *d_neg,
+                        float *d_loss /* NULL or [n_steps][n_new_users] */, void *stream);
 
 /* Measurement support (the reference has none; examples/bloom_embeddings/performance.py
  * times fit() with time.time()): when enabled, every launch of the engine's kernels is

@@ -74,6 +74,8 @@ _PROTOTYPES = {
                                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     'slk_bilinear_reserve': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_int64, C.c_int64,
                                        C.c_int32, C.c_int32, C.c_void_p]),
+    'slk_bilinear_foldin': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_bilinear_predict': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'slk_poolnet_train': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_int64, C.c_void_p,
@@ -393,6 +395,14 @@ class Engine(object):
         self._check(self._lib.slk_bilinear_reserve(
             self._ctx, C.byref(tables), C.byref(optim), int(n), int(batch_size),
             LOSS_KINDS[loss] if isinstance(loss, str) else int(loss), int(n_neg), stream))
+
+    def bilinear_foldin(self, tables, optim, d_off, d_items, n_new_users, n, loss, n_neg, n_steps, d_neg, d_loss=None, stream=0):
+        """include/spotlight_hip.h: slk_bilinear_foldin -- n_steps optimizer steps on the NEW users' rows and biases
+        (tables.d_param[0] / [2], optim state slots 0 / 2) from their histories d_off[n_new_users + 1] / d_items[n] and the
+        negatives d_neg[n_steps][nn][n], the item tables frozen; d_loss: None or [n_steps][n_new_users]."""
+        self._check(self._lib.slk_bilinear_foldin(
+            self._ctx, C.byref(tables), C.byref(optim), d_off, d_items, int(n_new_users), int(n),
+            LOSS_KINDS[loss] if isinstance(loss, str) else int(loss), int(n_neg), int(n_steps), d_neg, d_loss, stream))
 
     def bilinear_predict(self, tables, d_users, n_users, d_items, n, d_out, stream=0):
         self._check(self._lib.slk_bilinear_predict(self._ctx, C.byref(tables), d_users, int(n_users),

@@ -256,6 +256,11 @@ const slk_opt_desc slk_eval_options[] = {
      [](slk_ctx *c, int64_t v) { c->opt_topk_items_per_wg = v; }},
     {"eval_items_per_wg", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_eval_items_per_wg; },
      [](slk_ctx *c, int64_t v) { c->opt_eval_items_per_wg = v; }},
+    // slk_bilinear_foldin's route choice: no row of the table above either (training never reads it).  The two routes add a
+    // user's gradient terms in different orders, so the value is NOT bit-neutral; tests/foldin_checks.py runs every check under
+    // the default, all-workgroup and all-wave
+    {"foldin_wg_min_len", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_foldin_wg_min_len; },
+     [](slk_ctx *c, int64_t v) { c->opt_foldin_wg_min_len = v; }},
 };
 const slk_opt_desc *slk_find_option(const char *name) {
     for (const slk_opt_desc &d : slk_options)

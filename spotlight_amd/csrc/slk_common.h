@@ -237,6 +237,8 @@ struct slk_ctx {
     int64_t opt_eval_items_per_wg = 0;  // slk_*_scores / slk_*_rank / predict over every item / slk_shard_scores / _rank_counts: items per
                                       // workgroup of the writing and the counting sweep (0: cut by the device's CU count, eval_gemm);
                                       // the same kind of switch
+    int64_t opt_foldin_wg_min_len = 0;  // slk_bilinear_foldin: histories of at least this many interactions take the workgroup route (0: the
+                                      // measured default, SLK_FOLDIN_WG_MIN_LEN in slk_foldin.hip); a test / measurement switch
     int opt_user_bias_zero_hint = 1;  // 1: honour SLK_TABLES_USER_BIAS_ZERO (0: fetch the user biases regardless -- A/B and test switch)
     int64_t opt_record_nt_min_bytes = (int64_t)192 << 20;  // records of a minibatch from this size on are stored non-temporally
                                    // (slk_bilinear.hip::do_passes; 0: never)

@@ -153,6 +153,14 @@ class ExplicitFactorizationModel(ImplicitFactorizationModel):
                 self._random_state.set_state(state_after_epoch)
                 raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
 
+    def fold_in(self, interactions, n_iter=None, init=None, negatives=None):
+        raise NotImplementedError('fold_in() of the explicit-feedback model is not built (INTEGRATION.md 2m): its step needs the new '
+                                  "users' ratings and has no negatives")
+
+    def recommend_vectors(self, embeddings, biases=None, k=10, exclude=None):
+        raise NotImplementedError('recommend_vectors() of the explicit-feedback model is not built (INTEGRATION.md 2m): it goes with '
+                                  'fold_in()')
+
     def predict(self, user_ids, item_ids=None):
         """Predicted ratings for one user against all/some items, or for explicit (user, item) pairs:
         exp() of the score under the poisson loss, sigmoid() under the logistic one (explicit.py:245-284)."""

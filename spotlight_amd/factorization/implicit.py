@@ -851,6 +851,45 @@ class ImplicitFactorizationModel(object):
                                           _stream_for(device))
         return items.cpu().numpy(), scores.cpu().numpy()
 
+    def fold_in(self, interactions, n_iter=None, init=None, negatives=None):
+        """Rows for users who arrived after fit(): (embeddings float32 [H, dim], biases float32 [H]) learned from the new users'
+        own histories with the item parameters FROZEN.  The model is not modified (its RandomState is consumed, see below);
+        recommend_vectors() serves the users from these rows.
+
+        `interactions`: the new users' (user, item) pairs; the user ids label the new users 0 .. H - 1 (H =
+        interactions.num_users), the item ids are the model's.  Duplicates are kept, the order within a user is the order of
+        appearance.  One step of user u is one reference minibatch made of u's interactions alone (mean over them), one
+        optimizer step on u's row and bias -- so a user's result does not depend on who else is in the call.  A user without
+        interactions keeps their initial row.
+        `n_iter`: steps (default: the model's).  `init`: None draws the rows from the model's RandomState as fit() initialises
+        them (normal(0, 1 / dim); zero biases) -- before the negatives --, or an (embeddings, biases) pair.  `negatives`: None
+        draws them on the device from the model's RandomState, consuming the stream exactly as n_iter successive
+        sample_items(num_items, (nn, n)) calls would (nn = num_negative_samples under adaptive hinge, else 1); an array
+        [n_iter, nn, n] (columns in history order: sorted by user, stable) is used as given and leaves the RandomState alone.
+        A fresh optimizer of the model's own kind and hyper-parameters (optimizer_func) is created for the new rows.
+
+        Plain tables with Adam / Adagrad / SparseAdam / plain SGD: one fused call (csrc/slk_foldin.hip).  An item
+        BloomEmbedding (materialised once), any other optimizer_func, or a custom representation with `item_embeddings` /
+        `item_biases`: the same steps through autograd (spotlight_amd/foldin.py).  A user BloomEmbedding has no per-user row:
+        TypeError.  Refused inside an open fit() scope whose item biases are shadowed, as predict() is."""
+        from spotlight_amd import foldin as _foldin
+        return _foldin.fold_in(self, interactions, n_iter, init, negatives)
+
+    def _fold_in_generic(self, interactions, n_iter=None, init=None, negatives=None):
+        """fold_in() through the generic route whatever the model (what the tests compare the fused route with)."""
+        from spotlight_amd import foldin as _foldin
+        return _foldin.fold_in(self, interactions, n_iter, init, negatives, generic=True)
+
+    def recommend_vectors(self, embeddings, biases=None, k=10, exclude=None):
+        """recommend() for user VECTORS (fold_in()'s rows, or any [n, dim] array; `biases` default 0): the k best items of every
+        row, in recommend()'s order, padding, exclusion forms (None, a sparse matrix / Interactions whose row r lists row r's
+        items, one index array per row) and outputs.  The score of (row, item) is predict()'s: (dot + bias) + item bias, so the
+        model's own trained rows give recommend()'s arrays bit for bit.  k <= TOPK_K_MAX on a plain item table selects inside
+        the scoring sweep (slk_shard_topk over the item side alone); a larger k, or an item BloomEmbedding (materialised once),
+        sorts score rows a tile at a time."""
+        from spotlight_amd import foldin as _foldin
+        return _foldin.recommend_vectors(self, embeddings, biases, k, exclude)
+
     def _embedding_table(self, attr, num_rows):
         """The dense float32 [num_rows, dim] device tensor behind the net's `attr` layer: a plain layer's weight in place; a
         BloomEmbedding's representation of id j (the sum of its hashed rows) materialised once with the module's own forward on

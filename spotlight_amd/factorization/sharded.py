@@ -649,6 +649,14 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
             return items.cpu().numpy(), scores.cpu().numpy()
         return _rec.merge_topk(items.cpu().numpy(), scores.cpu().numpy(), k)
 
+    def fold_in(self, interactions, n_iter=None, init=None, negatives=None):
+        raise NotImplementedError('fold_in() of the row-sharded model is not built (INTEGRATION.md 2m): every rank holds a shard of '
+                                  'the item rows, so a new user\'s step would need the rows\' owners')
+
+    def recommend_vectors(self, embeddings, biases=None, k=10, exclude=None):
+        raise NotImplementedError('recommend_vectors() of the row-sharded model is not built (INTEGRATION.md 2m): it goes with '
+                                  'fold_in()')
+
     def similar_users(self, user_ids, k=10, metric='cosine', exclude_self=True, exclude=None):
         raise NotImplementedError('similar_users() of the row-sharded model is not built (INTEGRATION.md 2l): user rows are '
                                   'sharded as item rows are and it would mirror similar_items()')
