@@ -1043,18 +1043,78 @@ SLK_EXPORT int slk_bilinear_predict(slk_ctx *ctx, const slk_tables *tables, cons
     return SLK_OK;
 }
 
-static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim,
-                               const int64_t *d_users, const int64_t *d_items, int64_t n,
-                               int64_t batch_size, int32_t loss, int32_t n_neg, const int64_t *d_neg_in,
-                               int64_t *d_neg_out, float *d_mb_loss, void *stream, bool reserve_only,
-                               const float *d_ratings = nullptr, bool prefetch_only = false);
+// ---------------------------------------------------------------------------------------------------------------------------
+// The training driver.  A call is (1) taken down as given (train_call), (2) planned: every derived value and every refusal,
+// before any GPU work (plan_training), (3) given its scratch (ensure_scratch; slk_bilinear_reserve stops behind it), (4) its
+// kernels (pick_kernels), and (5) scheduled: chunk by chunk, the value-independent prep of a chunk (prep_sample, prep_sort)
+// and its minibatches (run_chunk: score_stage, user_stage, item_stage) in line (run_inline), one chunk ahead
+// (run_pipelined), or the first chunk a whole call ahead (prefetch_first_chunk).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct train_call {  // the arguments as given (ratings: explicit feedback, and only it)
+    enum { TRAIN, RESERVE, PREFETCH } mode;
+    const slk_tables *tables;
+    slk_optim *optim;
+    const int64_t *users, *items;
+    const float *ratings;
+    const int64_t *neg_in;
+    int64_t *neg_out;
+    float *mb_loss;
+    int64_t n, batch_size;
+    int32_t loss, n_neg;
+    hipStream_t s;
+};
+
+struct train_plan {  // everything derived from a call and the ctx's options before any GPU work
+    int vec, g, D;
+    // RS: record = the pre-step user row (16-B granular; D = 64: two aligned 128-B lines); RSU: user-bloom gradient record (+ an
+    // unused bias slot); hot users (k_user_pass<..., ULONG>): two partials of UPS floats per tile of SLK_USER_TILE positions
+    int RS, RSU, UPS;
+    size_t utiles;
+    unsigned ubits, ibits, ucbits, icbits;
+    slk_bloom_dev ubd, ibd;  // BloomEmbedding layers (layers.py:74-244): keys of the row-owner passes are hashed rows
+    int Hu, Hi;
+    // expl: explicit feedback (ratings, no negatives); fused: ... whose user pass forms score, loss and dL/dscore itself (option
+    // "explicit_fused"); pre: dL/dscore is computed before the user pass
+    bool bloom, adaptive, expl, fused, pre, dense, late;
+    int nn, NP, umode, nsets;
+    int64_t bsz, mb_per_chunk, chunk_cap, occ_mult;
+    // chunk ck is [ck * chunk_cap, min(n, (ck + 1) * chunk_cap)): nc_max interactions in the largest (= the first); 0 chunks: an empty call
+    size_t nc_max, n_chunks;
+    // one_draw: the negatives of the WHOLE call are one draw of the sampler, not one per chunk; epoch_route: as planned -- the
+    // persistent route may still refuse its first launch (train_run)
+    bool side, pingpong, sgl_on, shadowed, one_draw, epoch_route;
+    size_t dense_elems[4];  // the *_DENSE optimizers' gradient buffers
+};
+
+struct train_run {  // what changes while a call runs
+    const uint32_t *neg_all;  // negatives of the whole call drawn ahead (ctx->pf_neg, ctx->call_neg): the chunks read theirs from it
+    int64_t mb_global;        // minibatches done
+    bool epoch_route;         // false from the first chunk on whose cooperative launch was refused
+};
+
+struct train_kernels {
+    pass_fn upass, spass, upass_lat, upass_long, upass_lat_long, ustitch, upass_sgl;
+    slk_item_fns ipass, ipass_rows, ipass_bias, rpass_rows, ipass_sgl;
+    unsigned gpb;
+    int occ_user, occ_sgl;
+};
+
+static inline uint32_t *u32p(const slk_buf &b) { return (uint32_t *)b.p; }
+static inline float *f32p(const slk_buf &b) { return (float *)b.p; }
+static inline int64_t chunk_begin(const train_plan &p, size_t ck) { return (int64_t)ck * p.chunk_cap; }
+static inline uint32_t chunk_len(const train_plan &p, const train_call &c, size_t ck) {
+    const int64_t c1 = chunk_begin(p, ck + 1);
+    return (uint32_t)((c1 < c.n ? c1 : c.n) - chunk_begin(p, ck));
+}
+
+static int run_training(slk_ctx *ctx, const train_call &c);
 
 SLK_EXPORT int slk_bilinear_train(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim,
                                   const int64_t *d_users, const int64_t *d_items, int64_t n,
                                   int64_t batch_size, int32_t loss, int32_t n_neg, const int64_t *d_neg_in,
                                   int64_t *d_neg_out, float *d_mb_loss, void *stream) {
-    return bilinear_train_impl(ctx, tables, optim, d_users, d_items, n, batch_size, loss, n_neg, d_neg_in,
-                               d_neg_out, d_mb_loss, stream, false);
+    return run_training(ctx, {train_call::TRAIN, tables, optim, d_users, d_items, nullptr, d_neg_in, d_neg_out, d_mb_loss, n,
+                              batch_size, loss, n_neg, (hipStream_t)stream});
 }
 
 SLK_EXPORT int slk_bilinear_reserve(slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, int64_t n,
@@ -1062,8 +1122,8 @@ SLK_EXPORT int slk_bilinear_reserve(slk_ctx *ctx, const slk_tables *tables, cons
     slk_optim o;
     if (!optim) return slk_fail(ctx, SLK_EINVAL, "optim is NULL");
     o = *optim;
-    return bilinear_train_impl(ctx, tables, &o, nullptr, nullptr, n, batch_size, loss, n_neg, nullptr, nullptr,
-                               nullptr, stream, true);
+    return run_training(ctx, {train_call::RESERVE, tables, &o, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, batch_size,
+                              loss, n_neg, (hipStream_t)stream});
 }
 
 // The FIRST chunk of the next slk_bilinear_train call with these very arguments, prepared now: its negatives and sorts go to
@@ -1084,8 +1144,8 @@ SLK_EXPORT int slk_bilinear_prefetch(slk_ctx *ctx, const slk_tables *tables, con
         if (rc) return rc;
     }
     slk_optim o = *optim;
-    return bilinear_train_impl(ctx, tables, &o, d_users, d_items, n, batch_size, loss, n_neg, nullptr, nullptr, nullptr, stream,
-                               false, nullptr, true);
+    return run_training(ctx, {train_call::PREFETCH, tables, &o, d_users, d_items, nullptr, nullptr, nullptr, nullptr, n, batch_size,
+                              loss, n_neg, (hipStream_t)stream});
 }
 
 // ExplicitFactorizationModel.fit's minibatch loop (spotlight/factorization/explicit.py:213-236): the same
@@ -1097,74 +1157,81 @@ SLK_EXPORT int slk_bilinear_train_explicit(slk_ctx *ctx, const slk_tables *table
     if (ctx && (loss < SLK_LOSS_REGRESSION || loss > SLK_LOSS_LOGISTIC))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: loss kind %d is not regression/poisson/logistic", loss);
     if (ctx && n > 0 && !d_ratings) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: d_ratings is NULL");
-    return bilinear_train_impl(ctx, tables, optim, d_users, d_items, n, batch_size, loss, 0, nullptr, nullptr,
-                               d_mb_loss, stream, false, d_ratings);
+    return run_training(ctx, {train_call::TRAIN, tables, optim, d_users, d_items, d_ratings, nullptr, nullptr, d_mb_loss, n,
+                              batch_size, loss, 0, (hipStream_t)stream});
 }
 
-static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim,
-                               const int64_t *d_users, const int64_t *d_items, int64_t n,
-                               int64_t batch_size, int32_t loss, int32_t n_neg, const int64_t *d_neg_in,
-                               int64_t *d_neg_out, float *d_mb_loss, void *stream, bool reserve_only,
-                               const float *d_ratings, bool prefetch_only) {
-    if (!ctx) return SLK_EINVAL;
-    int vec, g, rc;
-    if ((rc = slk_check_tables(ctx, tables, 15u, &vec, &g, /*shadow_ok=*/true, /*pingpong_ok=*/true))) return rc;
+// Every derived value of a call and every refusal, in the order the rules have always been checked in (where a call breaks
+// several, the first one answers).  Touches nothing on the GPU; of the ctx only the current device and the noted stream.
+static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
+    train_plan &p = *plan;
+    const slk_tables *tables = c.tables;
+    const slk_optim *optim = c.optim;
+    const bool reserve = c.mode == train_call::RESERVE, prefetch = c.mode == train_call::PREFETCH;
+    const int64_t n = c.n;
+    int rc;
+    p.n_chunks = 0;
+    if ((rc = slk_check_tables(ctx, tables, 15u, &p.vec, &p.g, /*shadow_ok=*/true, /*pingpong_ok=*/true))) return rc;
     if ((rc = slk_check_optim(ctx, optim, 15u))) return rc;
-    if (n < 0 || batch_size < 1) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: n %lld batch_size %lld",
-                                                 (long long)n, (long long)batch_size);
-    if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_LOGISTIC)
-        return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", loss);
-    const bool adaptive = loss == SLK_LOSS_ADAPTIVE_HINGE;
-    const bool expl = loss >= SLK_LOSS_REGRESSION;  // explicit feedback: ratings, no negatives
-    if (expl != (d_ratings != nullptr) && !reserve_only)
+    if (n < 0 || c.batch_size < 1) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: n %lld batch_size %lld",
+                                                   (long long)n, (long long)c.batch_size);
+    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_LOGISTIC)
+        return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", c.loss);
+    p.adaptive = c.loss == SLK_LOSS_ADAPTIVE_HINGE;
+    p.expl = c.loss >= SLK_LOSS_REGRESSION;
+    if (p.expl != (c.ratings != nullptr) && !reserve)
         return slk_fail(ctx, SLK_EINVAL, "ratings go with (and only with) the regression/poisson/logistic losses");
-    const bool pre = adaptive || expl;  // dL/dscore is computed before the user pass
-    const int nn = adaptive ? n_neg : (expl ? 0 : 1);
-    if (!expl && (nn < 1 || nn > 1024)) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", nn);
-    const int NP = nn + 1;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    p.fused = p.expl && ctx->opt_explicit_fused;
+    p.pre = p.adaptive || p.expl;
+    p.umode = p.fused ? 2 : (p.pre ? 1 : 0);
+    p.nn = p.adaptive ? c.n_neg : (p.expl ? 0 : 1);
+    if (!p.expl && (p.nn < 1 || p.nn > 1024)) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", p.nn);
+    p.NP = p.nn + 1;
+    p.dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
     if (n == 0) return SLK_OK;
-    if (!reserve_only && (!d_users || !d_items || (!d_mb_loss && !prefetch_only)))
+    if (!reserve && (!c.users || !c.items || (!c.mb_loss && !prefetch)))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: NULL id/loss pointer");
-    if (batch_size * (int64_t)NP >= ((int64_t)1 << 31))
+    if (c.batch_size * (int64_t)p.NP >= ((int64_t)1 << 31))
         return slk_fail(ctx, SLK_EINVAL, "batch_size * (1 + negatives) must be < 2^31");
     SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
+    ctx->last_stream = c.s;
 
-    const int D = tables->dim;
-    const unsigned ubits = slk_bits_for((uint64_t)tables->num_users - 1);
-    const unsigned ibits = slk_bits_for((uint64_t)tables->num_items - 1);
-    unsigned idbits = ubits > ibits ? ubits : ibits;
-    // BloomEmbedding layers (layers.py:74-244): keys of the row-owner passes are hashed rows
-    slk_bloom_dev ubd, ibd;
-    slk_bloom_to_dev(tables->user_bloom, &ubd);
-    slk_bloom_to_dev(tables->item_bloom, &ibd);
-    const bool bloom = ubd.n_hash || ibd.n_hash;
-    const int Hu = ubd.n_hash, Hi = ibd.n_hash;
-    const unsigned ucbits = Hu ? slk_bits_for((uint64_t)ubd.rows) : 0;  // + the non-head sentinel row
-    const unsigned icbits = Hi ? slk_bits_for((uint64_t)ibd.rows - 1) : 0;
-    if (ucbits > idbits) idbits = ucbits;
-    if (icbits > idbits) idbits = icbits;
-    const int64_t occ_mult = (int64_t)NP * (Hi ? Hi : 1) > (int64_t)(Hu ? Hu : 1) ? (int64_t)NP * (Hi ? Hi : 1)
-                                                                                 : (int64_t)(Hu ? Hu : 1);
+    p.D = tables->dim;
+    p.ubits = slk_bits_for((uint64_t)tables->num_users - 1);
+    p.ibits = slk_bits_for((uint64_t)tables->num_items - 1);
+    unsigned idbits = p.ubits > p.ibits ? p.ubits : p.ibits;
+    slk_bloom_to_dev(tables->user_bloom, &p.ubd);
+    slk_bloom_to_dev(tables->item_bloom, &p.ibd);
+    p.bloom = p.ubd.n_hash || p.ibd.n_hash;
+    const int Hu = p.Hu = p.ubd.n_hash, Hi = p.Hi = p.ibd.n_hash;
+    p.ucbits = Hu ? slk_bits_for((uint64_t)p.ubd.rows) : 0;  // + the non-head sentinel row
+    p.icbits = Hi ? slk_bits_for((uint64_t)p.ibd.rows - 1) : 0;
+    if (p.ucbits > idbits) idbits = p.ucbits;
+    if (p.icbits > idbits) idbits = p.icbits;
+    p.occ_mult = (int64_t)p.NP * (Hi ? Hi : 1) > (int64_t)(Hu ? Hu : 1) ? (int64_t)p.NP * (Hi ? Hi : 1) : (int64_t)(Hu ? Hu : 1);
     // minibatches per chunk: keys must fit 32 bits, occurrences must fit 2^31, and scratch
     // stays bounded (~8M interactions).
-    const int64_t bsz = batch_size < n ? batch_size : n;
+    const int64_t bsz = p.bsz = c.batch_size < n ? c.batch_size : n;
     int64_t mb_per_chunk = (int64_t)1 << (32 - idbits);
     // ~8M interactions per chunk (option "chunk_interactions"): large enough for the sorts and the
     // MT19937 jump-ahead sampler to fill the GPU, small enough to bound the scratch
     const int64_t cap_inter = ctx->opt_chunk_interactions;
     if (mb_per_chunk * bsz > cap_inter) mb_per_chunk = cap_inter / bsz;
-    while (mb_per_chunk > 1 && mb_per_chunk * bsz * occ_mult >= ((int64_t)1 << 31)) mb_per_chunk >>= 1;
+    while (mb_per_chunk > 1 && mb_per_chunk * bsz * p.occ_mult >= ((int64_t)1 << 31)) mb_per_chunk >>= 1;
     if (mb_per_chunk < 1) mb_per_chunk = 1;
-    if (bsz * occ_mult >= ((int64_t)1 << 31))
+    if (bsz * p.occ_mult >= ((int64_t)1 << 31))
         return slk_fail(ctx, SLK_EINVAL, "batch_size * lookups per interaction must be < 2^31");
     // the persistent route (slk_epoch.hip) keeps per-(minibatch, workgroup) loss partials and counts barriers in 32 bits:
     // at most 2^13 minibatches per launch (16 MB of partials at 256 workgroups)
     const bool maybe_epoch = ctx->opt_epoch_kernel && !ctx->epoch_refused && bsz <= ctx->opt_epoch_max_batch;
     if (maybe_epoch && mb_per_chunk > ((int64_t)1 << 13)) mb_per_chunk = (int64_t)1 << 13;
-    const int64_t chunk_cap = mb_per_chunk * bsz;
+    p.mb_per_chunk = mb_per_chunk;
+    // chunks of chunk_cap.  Chunking is value-neutral: the negatives of a call are one contiguous draw however
+    // it is cut.  (Ramped chunks and a short first chunk for the overlapped prep were measured in round 3 and lost at every
+    // call length -- small chunks pay the sampler's jump-ahead and the sorts' fixed costs again: profiles/r03_c_*, r03_w_*.)
+    p.chunk_cap = mb_per_chunk * bsz;
+    p.nc_max = (size_t)(p.chunk_cap < n ? p.chunk_cap : n);
+    p.n_chunks = (size_t)((n + p.chunk_cap - 1) / p.chunk_cap);
 
     // Adaptive hinge: only the positive and the selected negative of a column carry a gradient, so
     // the item-side owner passes run over 2 live occurrences per interaction (sorted per minibatch,
@@ -1172,37 +1239,75 @@ static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim
     // of looked-up rows whose gradient is zero.
     // Below `adaptive_late_min_batch` interactions per minibatch the per-minibatch sort of the live occurrences (half a dozen
     // small launches) costs more than the dead occurrences it removes from the item pass: all 1+n are sorted once per chunk.
-    const bool late = adaptive && optim->kind != SLK_OPT_SPARSE_ADAM && (Hi > 0 || bsz >= ctx->opt_adaptive_late_min_batch);
-    // scratch.  With the "overlap_prep" option the value-independent part of a chunk (negatives,
-    // sort by user, sort by item) is prepared on a second HIP stream while the previous chunk's
-    // passes run, and those buffers exist twice (ctx->pb[0|1]).  What fit() sets for its epochs (profiles/r03_a_*, r03_b_*: with
-    // two of the user pass's eight workgroups per CU left to the prep stream the steady state of a run of training calls gains
-    // 1.5-4 %; round 1 had measured no gain with the pass holding every wave slot); off on a bare ctx (slk_common.h).
-    const size_t nc_max = (size_t)(chunk_cap < n ? chunk_cap : n);
-    // chunk boundaries: chunks of chunk_cap.  Chunking is value-neutral: the negatives of a call are one contiguous draw however
-    // it is cut.  (Ramped chunks and a short first chunk for the overlapped prep were measured in round 3 and lost at every
-    // call length -- small chunks pay the sampler's jump-ahead and the sorts' fixed costs again: profiles/r03_c_*, r03_w_*.)
-    std::vector<int64_t> cb;
-    cb.push_back(0);
-    while (cb.back() < n) {
-        const int64_t next = cb.back() + mb_per_chunk * bsz;
-        cb.push_back(next < n ? next : n);
-    }
-    const size_t n_chunks = cb.size() - 1;
+    p.late = p.adaptive && optim->kind != SLK_OPT_SPARSE_ADAM && (Hi > 0 || bsz >= ctx->opt_adaptive_late_min_batch);
     // Two buffer sets whenever a call has more than one chunk: chunk c + 1 is prepared (negatives, sorts) BEFORE chunk c's passes are
     // enqueued.  `side`: that preparation goes to the ctx's second stream and runs BESIDE the passes (option "overlap_prep", what
     // fit() sets).  Otherwise (a bare ctx; round 6) it goes to the caller's own stream, one chunk ahead: still one stream, every
-    // kernel alone on the GPU -- but the host's one wait per chunk (the long-run flags of do_sort) now falls while the GPU works on
+    // kernel alone on the GPU -- but the host's one wait per chunk (the long-run flags of prep_sort) now falls while the GPU works on
     // the next chunk's prep instead of idling (a bubble of ~40 us per chunk of 8 minibatches in rounds 1-5).
-    const bool side = ctx->opt_overlap_prep && n_chunks > 1 && bsz >= ctx->opt_overlap_min_batch;
-    const int nsets = n_chunks > 1 ? 2 : 1;
-    // (the single-occurrence flags of a chunk, when the call may take that path: decided below, sized here)
-    const bool sgl_maybe = ctx->pp_active && ctx->pp_src_u == tables->d_param[0] && !pre && !bloom && !dense &&
-                           optim->kind == SLK_OPT_ADAGRAD && ctx->opt_item_single_min_items > 0 &&
-                           tables->num_items >= ctx->opt_item_single_min_items;
-    for (int st = 0; st < nsets; ++st) {
+    p.side = ctx->opt_overlap_prep && p.n_chunks > 1 && bsz >= ctx->opt_overlap_min_batch;
+    p.nsets = p.n_chunks > 1 ? 2 : 1;
+    // The negatives of the WHOLE call in ONE draw (it is one contiguous draw however the call is chunked): the generator's
+    // jump-ahead, ~130 us whatever the draw's length, is paid once per call instead of once per chunk (round 6: 0.0135 -> 0.0065
+    // ms per C2 step at 20 minibatches per call).  Calls of >= 2^30 draws and calls that are handed their negatives keep
+    // drawing / converting by chunk.
+    p.one_draw = !c.neg_in && p.nn > 0 && p.n_chunks > 1 && (uint64_t)n * (uint64_t)p.nn < ((uint64_t)1 << 30);
+    p.RS = (p.D + 3) / 4 * 4;
+    p.UPS = p.RS + 4;
+    p.utiles = ((size_t)bsz + SLK_USER_TILE - 1) / SLK_USER_TILE;
+    p.RSU = p.D + 4;
+    // user-row ping-pong of a training scope (slk_user_pingpong_begin): pair mode over plain tables with a row-sparse optimizer on
+    // the launch path -- the user pass writes the updated row to the other copy and no record, the item pass gathers the pre-step
+    // row from the copy the user pass read.  A call the scope cannot serve is refused, not trained beside it.
+    p.pingpong = ctx->pp_active && ctx->pp_src_u == tables->d_param[0];
+    if (ctx->pp_active && !p.pingpong && !reserve)
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: a user-row ping-pong (slk_user_pingpong_begin) is open on this ctx for OTHER "
+                                         "tables; close it (slk_user_pingpong_end / _abort) before training another model");
+    if (p.pingpong && (p.pre || p.bloom || p.dense || tables->num_users != ctx->pp_rows || p.D != ctx->pp_dim))
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: the user rows are ping-ponged (slk_user_pingpong_begin): only the pair losses "
+                                         "(pointwise, bpr, hinge) over plain tables of the scope's shape with a row-sparse optimizer train inside the scope");
+    // The single-occurrence fast path (k_user_pass<..., SGL>): inside a ping-pong scope, row-sparse Adagrad, item tables of at
+    // least "item_single_min_items" rows (default 2^24: a catalogue far larger than a minibatch, where nearly every occurrence is
+    // the only one of its item; at C2 -- two occurrences per item on average -- 12 % qualify and the flags would cost more)
+    // (a call that got here with `pingpong` has a pair loss, plain tables and a row-sparse optimizer: the refusal above)
+    p.sgl_on = p.pingpong && optim->kind == SLK_OPT_ADAGRAD && ctx->opt_item_single_min_items > 0 &&
+               tables->num_items >= ctx->opt_item_single_min_items;
+    // the item-bias shadow of a training scope (slk_bias_shadow_begin): the launch path's kernels index it, the persistent
+    // kernel does not -- a call whose biases are shadowed takes the launches
+    p.shadowed = ctx->shadow_active && ctx->shadow_src_p == tables->d_param[3] && !p.dense &&
+                 optim->kind == SLK_OPT_ADAGRAD && ctx->shadow_src_s == optim->d_state1[3];
+    if (ctx->shadow_active && !p.shadowed && ctx->shadow_src_p == tables->d_param[3])
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: the item biases are shadowed (slk_bias_shadow_begin) for another optimizer state");
+    // One scope per ctx, and the scope is a TRAINING scope of ONE model (ABI 11): a training call on other tables while it is
+    // open is a caller that has lost track of the scope -- refused, not trained beside it (the scope's _end would otherwise
+    // write through pointers whose owner may have moved on).  slk_bilinear_reserve allocates only and stays allowed.
+    if (ctx->shadow_active && !p.shadowed && !reserve)
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: an item-bias shadow (slk_bias_shadow_begin) is open on this ctx for OTHER "
+                                         "tables; close it (slk_bias_shadow_end / _abort) before training another model");
+    // minibatches of a few thousand interactions: every minibatch of a chunk inside ONE persistent launch (slk_epoch.hip)
+    p.epoch_route = !p.shadowed && !p.pingpong && (!p.pre || p.adaptive || p.fused) &&
+                    slk_epoch_eligible(ctx, tables, optim, bsz, c.loss, p.bloom);
+    p.dense_elems[0] = (size_t)(Hu ? p.ubd.rows : tables->num_users) * p.D;
+    p.dense_elems[1] = (size_t)(Hi ? p.ibd.rows : tables->num_items) * p.D;
+    p.dense_elems[2] = (size_t)tables->num_users;
+    p.dense_elems[3] = (size_t)tables->num_items;
+    return SLK_OK;
+}
+
+static int ensure_dense_buffers(slk_ctx *ctx, const train_plan &p, hipStream_t s) { return slk_ensure_dgrad(ctx, p.dense_elems, 15u, s); }
+
+// scratch.  With the "overlap_prep" option the value-independent part of a chunk (negatives,
+// sort by user, sort by item) is prepared on a second HIP stream while the previous chunk's
+// passes run, and those buffers exist twice (ctx->pb[0|1]).  What fit() sets for its epochs (profiles/r03_a_*, r03_b_*: with
+// two of the user pass's eight workgroups per CU left to the prep stream the steady state of a run of training calls gains
+// 1.5-4 %; round 1 had measured no gain with the pass holding every wave slot); off on a bare ctx (slk_common.h).
+static int ensure_scratch(slk_ctx *ctx, const train_plan &p, hipStream_t s) {
+    const size_t nc_max = p.nc_max, NP = (size_t)p.NP, Hi = (size_t)p.Hi, Hu = (size_t)p.Hu, bsz = (size_t)p.bsz;
+    const bool late = p.late;
+    int rc;
+    for (int st = 0; st < p.nsets; ++st) {
         slk_prep_bufs &pb = ctx->pb[st];
-        if ((rc = slk_ensure(ctx, pb.neg32, nc_max * nn * 4))) return rc;
+        if ((rc = slk_ensure(ctx, pb.neg32, nc_max * p.nn * 4))) return rc;
         for (int b = 0; b < 2; ++b) {
             if ((rc = slk_ensure(ctx, pb.ukey[b], nc_max * 4))) return rc;
             if ((rc = slk_ensure(ctx, pb.uval[b], nc_max * 8))) return rc;
@@ -1215,634 +1320,595 @@ static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim
             if (Hu && (rc = slk_ensure(ctx, pb.buk[b], nc_max * Hu * 4))) return rc;
             if (Hu && (rc = slk_ensure(ctx, pb.bup[b], nc_max * Hu * 4))) return rc;
         }
-        if (pre && (rc = slk_ensure(ctx, pb.uit, nc_max * NP * 4))) return rc;
-        if (sgl_maybe && (rc = slk_ensure(ctx, pb.mflag, nc_max * NP + 16))) return rc;   // "occurs more than once" per occurrence: by payload,
-        if (sgl_maybe && (rc = slk_ensure(ctx, pb.msorted, nc_max * NP + 16))) return rc; //   in item-sorted order
-        if ((rc = slk_ensure(ctx, pb.lflags, 2 * (size_t)mb_per_chunk * 4))) return rc;  // long-run flags of a chunk: items, users
+        if (p.pre && (rc = slk_ensure(ctx, pb.uit, nc_max * NP * 4))) return rc;
+        if (p.sgl_on && (rc = slk_ensure(ctx, pb.mflag, nc_max * NP + 16))) return rc;    // "occurs more than once" per occurrence: by payload,
+        if (p.sgl_on && (rc = slk_ensure(ctx, pb.msorted, nc_max * NP + 16))) return rc;  //   in item-sorted order
+        if ((rc = slk_ensure(ctx, pb.lflags, 2 * (size_t)p.mb_per_chunk * 4))) return rc;  // long-run flags of a chunk: items, users
     }
-    const int RS = (D + 3) / 4 * 4;  // record = the pre-step user row (16-B granular; D = 64: two aligned 128-B lines)
-    if ((rc = slk_ensure(ctx, ctx->snap, (size_t)bsz * RS * 4))) return rc;
-    // user-row ping-pong of a training scope (slk_user_pingpong_begin): pair mode over plain tables with a row-sparse optimizer on
-    // the launch path -- the user pass writes the updated row to the other copy and no record, the item pass gathers the pre-step
-    // row from the copy the user pass read.  A call the scope cannot serve is refused, not trained beside it.
-    const bool pingpong = ctx->pp_active && ctx->pp_src_u == tables->d_param[0];
-    if (ctx->pp_active && !pingpong && !reserve_only)
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: a user-row ping-pong (slk_user_pingpong_begin) is open on this ctx for OTHER "
-                                         "tables; close it (slk_user_pingpong_end / _abort) before training another model");
-    if (pingpong && (pre || bloom || dense || tables->num_users != ctx->pp_rows || D != ctx->pp_dim))
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: the user rows are ping-ponged (slk_user_pingpong_begin): only the pair losses "
-                                         "(pointwise, bpr, hinge) over plain tables of the scope's shape with a row-sparse optimizer train inside the scope");
-    // The single-occurrence fast path (k_user_pass<..., SGL>): inside a ping-pong scope, row-sparse Adagrad, item tables of at
-    // least "item_single_min_items" rows (default 2^24: a catalogue far larger than a minibatch, where nearly every occurrence is
-    // the only one of its item; at C2 -- two occurrences per item on average -- 12 % qualify and the flags would cost more)
-    const bool sgl_on = pingpong && optim->kind == SLK_OPT_ADAGRAD && ctx->opt_item_single_min_items > 0 &&
-                        tables->num_items >= ctx->opt_item_single_min_items;
+    if ((rc = slk_ensure(ctx, ctx->snap, bsz * p.RS * 4))) return rc;
     // dL/dscore per (position, pair); ping-pong: {dL/dscore, src} per (position, pair)
-    if ((rc = slk_ensure(ctx, ctx->extra[BL_GSN], (size_t)bsz * NP * (pingpong ? 8 : 4)))) return rc;
+    if ((rc = slk_ensure(ctx, ctx->extra[BL_GSN], bsz * NP * (p.pingpong ? 8 : 4)))) return rc;
     const unsigned max_grid = (unsigned)ctx->num_cus * (unsigned)(ctx->opt_user_grid_mult > 8 ? ctx->opt_user_grid_mult : 8);
     if ((rc = slk_ensure(ctx, ctx->losspart, (size_t)max_grid * 8))) return rc;
-    if (pre) {
+    if (p.pre) {
         if ((rc = slk_ensure(ctx, ctx->gk, nc_max * NP * 4))) return rc;
         if ((rc = slk_ensure(ctx, ctx->sk, nc_max * NP * 4))) return rc;
     }
     if (late) {
         // (the live lists are sorted per minibatch on the PASSES' stream; with the overlapped prep another chunk's sorts run on
         // the prep stream at the same time, so these sorts have temporary storage of their own: BL_LATE_SORT, not ctx->sort_tmp)
-        const size_t nl = 2 * (size_t)bsz, nlh = nl * (size_t)(Hi ? Hi : 1);
+        const size_t nl = 2 * bsz, nlh = nl * (Hi ? Hi : 1);
         if ((rc = slk_ensure(ctx, ctx->extra[BL_LIVE], nl * 4))) return rc;
         for (int b = 0; b < 4; ++b)
             if ((rc = slk_ensure(ctx, ctx->extra[BL_LK0 + b], nlh * 4))) return rc;
     }
-    // hot users (k_user_pass<..., ULONG>): two partials per tile of SLK_USER_TILE positions, metas + the long-run counter
-    const int UPS = RS + 4;
-    const size_t utiles = ((size_t)bsz + SLK_USER_TILE - 1) / SLK_USER_TILE;
-    if (!bloom) {
-        if ((rc = slk_ensure(ctx, ctx->extra[BL_UPART], 2 * utiles * (size_t)UPS * 4))) return rc;
-        const size_t meta_bytes = 2 * utiles * 8 + 64;
+    if (!p.bloom) {
+        if ((rc = slk_ensure(ctx, ctx->extra[BL_UPART], 2 * p.utiles * (size_t)p.UPS * 4))) return rc;
+        const size_t meta_bytes = 2 * p.utiles * 8 + 64;
         if (meta_bytes > ctx->upart_meta.cap) {
             if ((rc = slk_ensure(ctx, ctx->upart_meta, meta_bytes))) return rc;
             SLK_HIP(ctx, hipMemsetAsync(ctx->upart_meta.p, 0, ctx->upart_meta.cap, s));  // stamp 0 is never used
         }
     }
-    const int RSU = D + 4;  // user-bloom gradient record (+ an unused bias slot)
-    if (Hu && (rc = slk_ensure(ctx, ctx->extra[BL_UREC], (size_t)bsz * RSU * 4))) return rc;
-    // minibatches of a few thousand interactions: every minibatch of a chunk inside ONE persistent launch (slk_epoch.hip)
-    // the item-bias shadow of a training scope (slk_bias_shadow_begin): the launch path's kernels index it, the persistent
-    // kernel does not -- a call whose biases are shadowed takes the launches
-    const bool shadowed = ctx->shadow_active && ctx->shadow_src_p == tables->d_param[3] && !dense &&
-                          optim->kind == SLK_OPT_ADAGRAD && ctx->shadow_src_s == optim->d_state1[3];
-    if (ctx->shadow_active && !shadowed && ctx->shadow_src_p == tables->d_param[3])
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: the item biases are shadowed (slk_bias_shadow_begin) for another optimizer state");
-    // One scope per ctx, and the scope is a TRAINING scope of ONE model (ABI 11): a training call on other tables while it is
-    // open is a caller that has lost track of the scope -- refused, not trained beside it (the scope's _end would otherwise
-    // write through pointers whose owner may have moved on).  slk_bilinear_reserve allocates only and stays allowed.
-    if (ctx->shadow_active && !shadowed && !reserve_only)
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: an item-bias shadow (slk_bias_shadow_begin) is open on this ctx for OTHER "
-                                         "tables; close it (slk_bias_shadow_end / _abort) before training another model");
-    if (shadowed && !prefetch_only && !reserve_only) ++ctx->stat_shadowed;
-    if (pingpong && !prefetch_only && !reserve_only) ++ctx->stat_pingpong;
-    bool epoch_route = !shadowed && !pingpong && (!pre || adaptive || (expl && ctx->opt_explicit_fused)) && slk_epoch_eligible(ctx, tables, optim, bsz, loss, bloom);
-    auto ensure_dense_buffers = [&]() -> int {
-        const size_t elems[4] = {(size_t)(Hu ? ubd.rows : tables->num_users) * D,
-                                 (size_t)(Hi ? ibd.rows : tables->num_items) * D, (size_t)tables->num_users,
-                                 (size_t)tables->num_items};
-        return slk_ensure_dgrad(ctx, elems, 15u, s);
-    };
-    if (dense && !epoch_route && (rc = ensure_dense_buffers())) return rc;
+    if (Hu && (rc = slk_ensure(ctx, ctx->extra[BL_UREC], bsz * p.RSU * 4))) return rc;
+    if (p.dense && !p.epoch_route && (rc = ensure_dense_buffers(ctx, p, s))) return rc;
+    return SLK_OK;
+}
 
-    if (reserve_only) {
-        if (side && (rc = slk_prep_stream_init(ctx))) return rc;
-        // the pinned read-back buffers and events of the long-run flags, per buffer set: hipHostMalloc inside a training call
-        // costs a device synchronisation (measured: the first overlapped call of a process 0.85 instead of 0.745 ms per step)
-        for (int st = 0; st < nsets; ++st) {
-            slk_prep_bufs &pb = ctx->pb[st];
-            if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)mb_per_chunk))) return rc;
-            pb.h_lflags_n = 0;
-            if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
-        }
-        if (side && !ctx->prep_warmed && nn > 0 && nc_max >= 4096) {
-            // One tiny prep on the prep stream, ordered against the caller's stream by the pipeline's own events: whatever the
-            // runtime sets up the first time these kernels (sampler, sorts) run on a stream and the first time two
-            // streams wait for each other's events then happens here and not inside the first overlapped training call
-            // (measured: that call ran 0.81-0.87 instead of 0.75-0.77 ms per step; a prior overlapped call of two minibatches
-            // removes it, profiles/r03_p_*).  The RNG state is put back afterwards.
-            hipStream_t ps = ctx->prep_stream;
-            slk_prep_bufs &pb = ctx->pb[1];
-            if ((rc = slk_ensure(ctx, ctx->extra[BL_LIVE], sizeof(slk_rng_dev) + 64))) return rc;
-            SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));
-            SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
-            SLK_HIP(ctx, hipMemcpyAsync(ctx->extra[BL_LIVE].p, ctx->d_rng, sizeof(slk_rng_dev), hipMemcpyDeviceToDevice, ps));
-            if ((rc = slk_sample_u32(ctx, tables->num_items, 4096, (uint32_t *)pb.neg32.p, nullptr, ps))) return rc;
-            SLK_HIP(ctx, hipMemcpyAsync(ctx->d_rng, ctx->extra[BL_LIVE].p, sizeof(slk_rng_dev), hipMemcpyDeviceToDevice, ps));
-            SLK_HIP(ctx, hipMemsetAsync(pb.ukey[0].p, 0, 4096 * 4, ps));
-            if ((rc = slk_sort_pairs_u32_u64(ctx, (const uint32_t *)pb.ukey[0].p, (uint32_t *)pb.ukey[1].p, (const uint64_t *)pb.uval[0].p,
-                                             (uint64_t *)pb.uval[1].p, 4096, 20, ps)))
-                return rc;
-            if (!late) {
-                SLK_HIP(ctx, hipMemsetAsync(pb.ikey[0].p, 0, 4096 * 4, ps));
-                if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)pb.ikey[0].p, (uint32_t *)pb.ikey[1].p, (const uint32_t *)pb.ipay[0].p,
-                                                 (uint32_t *)pb.ipay[1].p, 4096, 20, ps)))
-                    return rc;
-            }
-            SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[1], ps));
-            SLK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_prep[1], 0));
-            SLK_HIP(ctx, hipEventRecord(ctx->ev_done[1], s));
-            SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[1], 0));
-            SLK_HIP(ctx, hipStreamSynchronize(ps));
-            SLK_HIP(ctx, hipStreamSynchronize(s));
-            ctx->last_stream = s;
-            ctx->sampled_valid = false;
-            ctx->prep_warmed = true;
-        }
-        if (epoch_route && (rc = slk_epoch_reserve(ctx, tables, optim, (uint32_t)((nc_max + bsz - 1) / bsz), bsz, (int)loss, NP))) return rc;
-        // sampler and sort scratch for the largest chunk (the whole call when its negatives are one draw), so that the training
-        // call allocates nothing
-        const bool all_r = nn > 0 && n_chunks > 1 && (uint64_t)n * (uint64_t)nn < ((uint64_t)1 << 30);
-        if (all_r && (rc = slk_ensure(ctx, ctx->call_neg, (size_t)n * nn * 4))) return rc;
-        if ((rc = slk_sample_reserve(ctx, tables->num_items, all_r ? n * (int64_t)nn : (int64_t)nc_max * nn))) return rc;
-        return slk_sort_reserve(ctx, nc_max * (size_t)occ_mult);
+// One tiny prep on the prep stream, ordered against the caller's stream by the pipeline's own events: whatever the
+// runtime sets up the first time these kernels (sampler, sorts) run on a stream and the first time two
+// streams wait for each other's events then happens here and not inside the first overlapped training call
+// (measured: that call ran 0.81-0.87 instead of 0.75-0.77 ms per step; a prior overlapped call of two minibatches
+// removes it, profiles/r03_p_*).  The RNG state is put back afterwards.
+static int warm_prep_stream(slk_ctx *ctx, const train_plan &p, const train_call &c) {
+    hipStream_t s = c.s, ps = ctx->prep_stream;
+    slk_prep_bufs &pb = ctx->pb[1];
+    int rc;
+    if ((rc = slk_ensure(ctx, ctx->extra[BL_LIVE], sizeof(slk_rng_dev) + 64))) return rc;
+    SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));
+    SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
+    SLK_HIP(ctx, hipMemcpyAsync(ctx->extra[BL_LIVE].p, ctx->d_rng, sizeof(slk_rng_dev), hipMemcpyDeviceToDevice, ps));
+    if ((rc = slk_sample_u32(ctx, c.tables->num_items, 4096, u32p(pb.neg32), nullptr, ps))) return rc;
+    SLK_HIP(ctx, hipMemcpyAsync(ctx->d_rng, ctx->extra[BL_LIVE].p, sizeof(slk_rng_dev), hipMemcpyDeviceToDevice, ps));
+    SLK_HIP(ctx, hipMemsetAsync(pb.ukey[0].p, 0, 4096 * 4, ps));
+    if ((rc = slk_sort_pairs_u32_u64(ctx, u32p(pb.ukey[0]), u32p(pb.ukey[1]), (const uint64_t *)pb.uval[0].p, (uint64_t *)pb.uval[1].p,
+                                     4096, 20, ps)))
+        return rc;
+    if (!p.late) {
+        SLK_HIP(ctx, hipMemsetAsync(pb.ikey[0].p, 0, 4096 * 4, ps));
+        if ((rc = slk_sort_pairs_u32_u32(ctx, u32p(pb.ikey[0]), u32p(pb.ikey[1]), u32p(pb.ipay[0]), u32p(pb.ipay[1]), 4096, 20, ps)))
+            return rc;
     }
+    SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[1], ps));
+    SLK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_prep[1], 0));
+    SLK_HIP(ctx, hipEventRecord(ctx->ev_done[1], s));
+    SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[1], 0));
+    SLK_HIP(ctx, hipStreamSynchronize(ps));
+    SLK_HIP(ctx, hipStreamSynchronize(s));
+    ctx->last_stream = s;
+    ctx->sampled_valid = false;
+    ctx->prep_warmed = true;
+    return SLK_OK;
+}
 
-    const int upd = slk_upd_for(optim->kind);
-    pass_fn upass = nullptr, spass = nullptr, upass_lat = nullptr, upass_long = nullptr, upass_lat_long = nullptr, ustitch = nullptr;
-    pass_fn upass_sgl = nullptr;
-    slk_item_fns ipass = {nullptr, nullptr}, ipass_rows = ipass, ipass_bias = ipass, rpass_rows = ipass, ipass_sgl = ipass;
-    const int umode = (expl && ctx->opt_explicit_fused) ? 2 : (pre ? 1 : 0);
-#define SLK_PICK(V_, G_)                                                                  \
-    do {                                                                                  \
-        upass = user_pass_fn<V_, G_>(upd, umode, bloom);                                  \
-        if (umode == 0 && !bloom) upass_lat = user_pass_lat_fn<V_, G_>(upd);              \
-        if (umode == 0 && !bloom) upass_lat_long = user_pass_lat_fn<V_, G_, true>(upd);   \
-        if (!bloom) upass_long = user_pass_long_fn<V_, G_>(upd, umode);                   \
-        if (!bloom) ustitch = user_stitch_fn<V_, G_>(upd);                                \
-        ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP>(upd);                             \
-        spass = k_score_pass<V_, G_>;                                                     \
-        if (pingpong) {                                                                   \
-            upass = user_pass_pp_fn<V_, G_, false, false>(upd);                           \
-            upass_lat = user_pass_pp_fn<V_, G_, true, false>(upd);                        \
-            upass_long = user_pass_pp_fn<V_, G_, false, true>(upd);                       \
-            upass_lat_long = user_pass_pp_fn<V_, G_, true, true>(upd);                    \
-            ustitch = user_stitch_pp_fn<V_, G_>(upd);                                     \
-            ipass = item_pass_pp_fn<V_, G_>(upd);                                         \
-            if (sgl_on) {                                                                 \
-                upass_sgl = user_pass_sgl_fn<V_, G_>();                                   \
-                ipass_sgl = item_pass_sgl_fn<V_, G_>();                                   \
-            }                                                                             \
-        }                                                                                 \
-        if (bloom) {                                                                      \
-            ipass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP, SLK_PART_ROWS>(upd);     \
-            ipass_bias = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP, SLK_PART_BIAS>(upd);     \
-            rpass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_ROW, SLK_PART_ROWS>(upd);      \
-        }                                                                                 \
+// slk_bilinear_reserve: what a training call of this plan would otherwise allocate or set up on its way
+static int reserve_extras(slk_ctx *ctx, const train_plan &p, const train_call &c) {
+    int rc;
+    if (p.side && (rc = slk_prep_stream_init(ctx))) return rc;
+    // the pinned read-back buffers and events of the long-run flags, per buffer set: hipHostMalloc inside a training call
+    // costs a device synchronisation (measured: the first overlapped call of a process 0.85 instead of 0.745 ms per step)
+    for (int st = 0; st < p.nsets; ++st) {
+        slk_prep_bufs &pb = ctx->pb[st];
+        if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)p.mb_per_chunk))) return rc;
+        pb.h_lflags_n = 0;
+        if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
+    }
+    if (p.side && !ctx->prep_warmed && p.nn > 0 && p.nc_max >= 4096 && (rc = warm_prep_stream(ctx, p, c))) return rc;
+    const uint32_t n_mb = (uint32_t)((p.nc_max + p.bsz - 1) / p.bsz);
+    if (p.epoch_route && (rc = slk_epoch_reserve(ctx, c.tables, c.optim, n_mb, p.bsz, (int)c.loss, p.NP))) return rc;
+    // sampler and sort scratch for the largest chunk (the whole call when its negatives are one draw), so that the training
+    // call allocates nothing
+    if (p.one_draw && (rc = slk_ensure(ctx, ctx->call_neg, (size_t)c.n * p.nn * 4))) return rc;
+    if ((rc = slk_sample_reserve(ctx, c.tables->num_items, p.one_draw ? c.n * (int64_t)p.nn : (int64_t)p.nc_max * p.nn))) return rc;
+    return slk_sort_reserve(ctx, p.nc_max * (size_t)p.occ_mult);
+}
+
+static void pick_kernels(slk_ctx *ctx, const train_plan &p, const slk_optim *optim, train_kernels *kernels) {
+    train_kernels &k = *kernels;
+    const int upd = slk_upd_for(optim->kind), umode = p.umode;
+    const bool bloom = p.bloom;
+    k = train_kernels{};
+#define SLK_PICK(V_, G_)                                                                    \
+    do {                                                                                    \
+        k.upass = user_pass_fn<V_, G_>(upd, umode, bloom);                                  \
+        if (umode == 0 && !bloom) k.upass_lat = user_pass_lat_fn<V_, G_>(upd);              \
+        if (umode == 0 && !bloom) k.upass_lat_long = user_pass_lat_fn<V_, G_, true>(upd);   \
+        if (!bloom) k.upass_long = user_pass_long_fn<V_, G_>(upd, umode);                   \
+        if (!bloom) k.ustitch = user_stitch_fn<V_, G_>(upd);                                \
+        k.ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP>(upd);                             \
+        k.spass = k_score_pass<V_, G_>;                                                     \
+        if (p.pingpong) {                                                                   \
+            k.upass = user_pass_pp_fn<V_, G_, false, false>(upd);                           \
+            k.upass_lat = user_pass_pp_fn<V_, G_, true, false>(upd);                        \
+            k.upass_long = user_pass_pp_fn<V_, G_, false, true>(upd);                       \
+            k.upass_lat_long = user_pass_pp_fn<V_, G_, true, true>(upd);                    \
+            k.ustitch = user_stitch_pp_fn<V_, G_>(upd);                                     \
+            k.ipass = item_pass_pp_fn<V_, G_>(upd);                                         \
+            if (p.sgl_on) {                                                                 \
+                k.upass_sgl = user_pass_sgl_fn<V_, G_>();                                   \
+                k.ipass_sgl = item_pass_sgl_fn<V_, G_>();                                   \
+            }                                                                               \
+        }                                                                                   \
+        if (bloom) {                                                                        \
+            k.ipass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP, SLK_PART_ROWS>(upd);     \
+            k.ipass_bias = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP, SLK_PART_BIAS>(upd);     \
+            k.rpass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_ROW, SLK_PART_ROWS>(upd);      \
+        }                                                                                   \
     } while (0)
-    SLK_FOR_LAYOUT(vec, g, SLK_PICK);
+    SLK_FOR_LAYOUT(p.vec, p.g, SLK_PICK);
 #undef SLK_PICK
-    const unsigned gpb = 256u / (unsigned)g;
+    k.gpb = 256u / (unsigned)p.g;
     // The user pass is a grid-stride kernel: workgroups beyond what a CU holds RESIDENT start when others finish and unbalance
     // the pass.  Its grid is therefore capped at the kernel's own occupancy (slk_occupancy_of: the SparseAdam form needs 72
     // VGPRs = 7 workgroups per CU; launched 8 per CU it ran 0.58 ms, capped 0.44; Adagrad's 59 VGPRs hold 8).
     // (one cap for the forms a minibatch may take -- plain, latency-bound, long runs: the grid also counts the loss partials)
-    int occ_user = slk_occupancy_of(ctx, upass);
-    for (pass_fn f : {upass_lat, upass_long, upass_lat_long}) {
+    k.occ_user = slk_occupancy_of(ctx, k.upass);
+    for (pass_fn f : {k.upass_lat, k.upass_long, k.upass_lat_long}) {
         const int o = slk_occupancy_of(ctx, f);
-        if (o < occ_user) occ_user = o;
+        if (o < k.occ_user) k.occ_user = o;
     }
+    // (the single-occurrence form holds more registers than the four whose smallest occupancy caps the others: a cap of its own)
+    k.occ_sgl = p.sgl_on ? slk_occupancy_of(ctx, k.upass_sgl) : k.occ_user;
+}
 
-    // ---- prep of one chunk into buffer set `pb` (value-independent: ids only), in two halves:
-    // the negatives (ALU/latency-bound MT19937 generator), then the sorts (HBM-bound)
-    // negatives of the whole call drawn ahead by slk_bilinear_prefetch (ctx->pf_neg): the chunks read theirs from it
-    const uint32_t *neg_all = nullptr;
-    auto do_sample = [&](size_t ck, slk_prep_bufs &pb, hipStream_t s) -> int {
-        int rc;
-        const int64_t c0 = cb[ck];
-        const uint32_t nc = (uint32_t)(cb[ck + 1] - c0);
-        uint32_t *neg32 = (uint32_t *)pb.neg32.p;
-        if (neg_all) return SLK_OK;
+// ---- prep of one chunk into buffer set `pb` (value-independent: ids only), in two halves:
+// the negatives (ALU/latency-bound MT19937 generator), then the sorts (HBM-bound)
+static int prep_sample(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_run &run, size_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    const int64_t c0 = chunk_begin(p, ck);
+    const size_t nneg = (size_t)chunk_len(p, c, ck) * p.nn;
+    if (run.neg_all) return SLK_OK;
 
-        // ---- negatives (sampling.py:34, one randint per minibatch == one contiguous draw)
-        if (nn == 0) return SLK_OK;  // explicit feedback draws none
-        if (d_neg_in) {
-            slk_prof_begin(ctx, SLK_K_SAMPLE, s);
-            hipLaunchKernelGGL(k_i64_to_u32, dim3(slk_grid_for(ctx, (size_t)nc * nn, 256)), dim3(256), 0, s,
-                               d_neg_in + c0 * nn, neg32, (size_t)nc * nn);
-            SLK_LAUNCH_CHECK(ctx, "k_i64_to_u32");
-            if (d_neg_out)
-                SLK_HIP(ctx, hipMemcpyAsync(d_neg_out + c0 * nn, d_neg_in + c0 * nn, (size_t)nc * nn * 8,
-                                            hipMemcpyDeviceToDevice, s));
-            slk_prof_end(ctx, s);
-        } else {
-            if ((rc = slk_sample_u32(ctx, tables->num_items, (int64_t)nc * nn, neg32,
-                                     d_neg_out ? d_neg_out + c0 * nn : nullptr, s)))
-                return rc;
-        }
-        return SLK_OK;
-    };
-    auto do_sort = [&](size_t ck, slk_prep_bufs &pb, hipStream_t s) -> int {
-        int rc;
-        const int64_t c0 = cb[ck];
-        const uint32_t nc = (uint32_t)(cb[ck + 1] - c0);
-        const uint32_t nocc = nc * (uint32_t)NP;
-        const int64_t *cu = d_users + c0, *ci = d_items + c0;
-        const uint32_t *neg32 = neg_all ? neg_all + (size_t)c0 * nn : (const uint32_t *)pb.neg32.p;
-
-        // ---- prep: sort interactions by (minibatch, user), occurrences by (minibatch, item)
-        slk_prof_begin(ctx, SLK_K_PREP, s);
-        const unsigned mbbits = slk_bits_for((uint64_t)((nc - 1) / (uint32_t)bsz));
-        uint32_t *ukey_in = (uint32_t *)pb.ukey[0].p, *ukey = (uint32_t *)pb.ukey[1].p;
-        const uint32_t *uit, *uk = nullptr;
-        uint32_t *const ukeys[2] = {ukey_in, ukey};
-        if (!pre) {
-            // (keys and the fat (positive, negative) payload are formed by the sort's first pass from the id arrays)
-            uint64_t *const uvals[2] = {(uint64_t *)pb.uval[0].p, (uint64_t *)pb.uval[1].p};
-            if ((rc = slk_sort_user_fat(ctx, cu, ci, (const uint32_t *)neg32, nc, (size_t)bsz, ubits, mbbits, ukeys, uvals, s))) return rc;
-            uit = (const uint32_t *)pb.uval[1].p;  // little-endian (pos, neg) pairs
-        } else {
-            uint32_t *const uvals[2] = {(uint32_t *)pb.uval[0].p, (uint32_t *)pb.uval[1].p};
-            if ((rc = slk_sort_user_idx(ctx, cu, nc, (size_t)bsz, ubits, mbbits, ukeys, uvals, s))) return rc;
-            uk = (const uint32_t *)pb.uval[1].p;
-            hipLaunchKernelGGL(k_pack_items, dim3(slk_grid_for(ctx, nc, 256)), dim3(256), 0, s, uk, ci,
-                               (const uint32_t *)neg32, nc, nn, (uint32_t *)pb.uit.p);
-            SLK_LAUNCH_CHECK(ctx, "k_pack_items");
-            uit = (const uint32_t *)pb.uit.p;
-        }
-        if (late) {
-            hipLaunchKernelGGL(k_invert_perm, dim3(slk_grid_for(ctx, nc, 256)), dim3(256), 0, s, uk, nc,
-                               (uint32_t *)pb.ipay[0].p);
-            SLK_LAUNCH_CHECK(ctx, "k_invert_perm");
-        } else {
-            uint32_t *const ikeys[2] = {(uint32_t *)pb.ikey[0].p, (uint32_t *)pb.ikey[1].p};
-            uint32_t *const ivals[2] = {(uint32_t *)pb.ipay[0].p, (uint32_t *)pb.ipay[1].p};
-            if ((rc = slk_sort_item_occ(ctx, uit, nocc, (size_t)bsz, NP, ibits, mbbits, ikeys, ivals, s))) return rc;
-            if (sgl_on) {  // which occurrences are NOT the only one of their item in their minibatch (ids only)
-                SLK_HIP(ctx, hipMemsetAsync(pb.mflag.p, 0, (size_t)nocc, s));
-                hipLaunchKernelGGL(k_item_multi_flags, dim3(slk_grid_for(ctx, nocc, 256)), dim3(256), 0, s, (const uint32_t *)pb.ikey[1].p,
-                                   (const uint32_t *)pb.ipay[1].p, nocc, (uint32_t)bsz * (uint32_t)NP, (uint8_t *)pb.msorted.p,
-                                   (uint8_t *)pb.mflag.p);
-                SLK_LAUNCH_CHECK(ctx, "k_item_multi_flags");
-            }
-        }
-        // which minibatches hold a LONG run (an item run that wholly covers a tile of the item pass, [0, n_mb); a user run that
-        // wholly covers a tile of the user pass, [n_mb, 2 n_mb)): ids only, so the answer is fetched once per chunk and the usual
-        // minibatch (none) gets the plain passes with no stitch kernel behind them
-        if (!epoch_route) {  // (the persistent route walks the runs itself; its fall-back takes the long forms, do_passes)
-            const uint32_t n_mb_c = (nc + (uint32_t)bsz - 1) / (uint32_t)bsz;
-            if ((rc = slk_ensure(ctx, pb.lflags, 2 * (size_t)n_mb_c * 4))) return rc;
-            SLK_HIP(ctx, hipMemsetAsync(pb.lflags.p, 0, 2 * (size_t)n_mb_c * 4, s));
-            if (!late) {
-                hipLaunchKernelGGL(k_item_long_flags, dim3(slk_grid_for(ctx, nocc / (4 * gpb) + n_mb_c, 256)), dim3(256), 0, s,
-                                   (const uint32_t *)pb.ikey[1].p, nocc, (uint32_t)bsz * (uint32_t)NP, 4u * gpb,
-                                   (uint32_t)((1ull << ibits) - 1), 0xffffffffu, 0xffffffffu, (int *)pb.lflags.p);
-                SLK_LAUNCH_CHECK(ctx, "k_item_long_flags");
-            }
-            if (!bloom) {
-                hipLaunchKernelGGL(k_user_long_flags, dim3(slk_grid_for(ctx, nc / SLK_USER_TILE + n_mb_c, 256)), dim3(256), 0, s,
-                                   (const uint32_t *)ukey, nc, (uint32_t)bsz, (int *)pb.lflags.p + n_mb_c);
-                SLK_LAUNCH_CHECK(ctx, "k_user_long_flags");
-            }
-            if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)n_mb_c))) return rc;
-            SLK_HIP(ctx, hipMemcpyAsync(pb.h_lflags, pb.lflags.p, 2 * (size_t)n_mb_c * 4, hipMemcpyDeviceToHost, s));
-            if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
-            SLK_HIP(ctx, hipEventRecord(pb.ev_lflags, s));
-        } else {
-            pb.h_lflags_n = 0;  // no flags for this chunk: every pass of a fall-back takes the partial-writing form
-        }
-        if (Hi && !late) {
-            hipLaunchKernelGGL(k_build_item_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nocc * Hi, 256)), dim3(256), 0, s,
-                               uit, nocc, NP, (uint32_t)bsz, icbits, ibd, (uint32_t *)pb.bik[0].p,
-                               (uint32_t *)pb.bip[0].p);
-            SLK_LAUNCH_CHECK(ctx, "k_build_item_bloom_keys");
-            if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)pb.bik[0].p,
-                                             (uint32_t *)pb.bik[1].p,
-                                             (const uint32_t *)pb.bip[0].p,
-                                             (uint32_t *)pb.bip[1].p, (size_t)nocc * Hi, icbits + mbbits, s, true)))
-                return rc;
-        }
-        if (Hu) {
-            hipLaunchKernelGGL(k_build_user_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nc * Hu, 256)), dim3(256), 0, s,
-                               (const uint32_t *)ukey, (uint32_t)((1ull << ubits) - 1), nc, (uint32_t)bsz, ucbits, ubd,
-                               (uint32_t *)pb.buk[0].p, (uint32_t *)pb.bup[0].p);
-            SLK_LAUNCH_CHECK(ctx, "k_build_user_bloom_keys");
-            if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)pb.buk[0].p,
-                                             (uint32_t *)pb.buk[1].p,
-                                             (const uint32_t *)pb.bup[0].p,
-                                             (uint32_t *)pb.bup[1].p, (size_t)nc * Hu, ucbits + mbbits, s, true)))
-                return rc;
-        }
+    // ---- negatives (sampling.py:34, one randint per minibatch == one contiguous draw)
+    if (p.nn == 0) return SLK_OK;  // explicit feedback draws none
+    if (c.neg_in) {
+        slk_prof_begin(ctx, SLK_K_SAMPLE, s);
+        hipLaunchKernelGGL(k_i64_to_u32, dim3(slk_grid_for(ctx, nneg, 256)), dim3(256), 0, s, c.neg_in + c0 * p.nn, u32p(pb.neg32), nneg);
+        SLK_LAUNCH_CHECK(ctx, "k_i64_to_u32");
+        if (c.neg_out)
+            SLK_HIP(ctx, hipMemcpyAsync(c.neg_out + c0 * p.nn, c.neg_in + c0 * p.nn, nneg * 8, hipMemcpyDeviceToDevice, s));
         slk_prof_end(ctx, s);
-
         return SLK_OK;
-    };
-
-    int64_t mb_global = 0;
-    // ---- the minibatches of one prepared chunk, in order, on the caller's stream
-    auto do_passes = [&](size_t ck, slk_prep_bufs &pb) -> int {
-        int rc;
-        const int64_t c0 = cb[ck];
-        const uint32_t nc = (uint32_t)(cb[ck + 1] - c0);
-        const uint32_t *ukey = (const uint32_t *)pb.ukey[1].p;
-        const uint32_t *uit = pre ? (const uint32_t *)pb.uit.p : (const uint32_t *)pb.uval[1].p;
-        const uint32_t *uk = pre ? (const uint32_t *)pb.uval[1].p : nullptr;
-        bool lflags_ready = false;  // the chunk's long-run flags (do_sort): ONE host wait per chunk, before the first user pass
-        const uint32_t n_mb_c = (nc + (uint32_t)bsz - 1) / (uint32_t)bsz;
-        // ---- minibatches, in order
-        for (uint32_t b0 = 0; b0 < nc; b0 += (uint32_t)bsz, ++mb_global) {
-            const uint32_t b1 = (nc - b0 < (uint32_t)bsz) ? nc : b0 + (uint32_t)bsz;
-            const uint32_t bm = b1 - b0;
-            slk_pass_args a;
-            memset(&a, 0, sizeof(a));
-            for (int t = 0; t < 4; ++t) {
-                a.P[t] = tables->d_param[t];
-                a.S1[t] = dense ? (float *)ctx->dgrad[t].p : optim->d_state1[t];
-                a.S2[t] = optim->d_state2[t];
-            }
-            if (shadowed) {
-                a.P[3] = (float *)ctx->bias_shadow.p;
-                a.S1[3] = (float *)ctx->bias_shadow.p + 1;
-                a.bsh3 = 1u;
-            }
-            if (pingpong) {
-                a.P0alt = (float *)ctx->pp_alt.p;
-                a.uflag = (uint8_t *)ctx->pp_flags.p;
-            }
-            a.D = D;
-            a.NP = NP;
-            a.begin = b0;
-            a.end = b1;
-            a.ukey = ukey;
-            a.umask = (uint32_t)((1ull << ubits) - 1);
-            a.uit = uit;
-            a.uk = uk;
-            a.gk = (const float *)ctx->gk.p;
-            a.sk = (float *)ctx->sk.p;
-            a.snap = (float *)ctx->snap.p;
-            a.RS = RS;
-            a.gsn = (float *)ctx->extra[BL_GSN].p;
-            a.ikey = (const uint32_t *)pb.ikey[1].p;
-            a.imask = (uint32_t)((1ull << ibits) - 1);
-            a.ipay = (const uint32_t *)pb.ipay[1].p;
-            a.loss_partial = (double *)ctx->losspart.p;
-            a.mb_loss_out = d_mb_loss + mb_global;
-            a.loss_kind = loss;
-            a.inv_b = 1.0f / (float)bm;
-            a.ibegin = b0 * (uint32_t)NP;
-            a.iend = b1 * (uint32_t)NP;
-            a.pad_item = a.pad_item2 = 0xffffffffu;
-            a.ub = ubd;
-            a.ib = ibd;
-            a.urec = (float *)ctx->extra[BL_UREC].p;
-            a.RSU = RSU;
-            slk_set_opt_coeffs(a, optim);
-            // user biases the caller vouches are all zero, a loss whose user-bias gradient is exactly zero, an update for which a
-            // zero gradient is an exact no-op: nothing of the table is read or written by the pair-mode user pass
-            a.ubz = (tables->flags & SLK_TABLES_USER_BIAS_ZERO) && (loss == SLK_LOSS_BPR || loss == SLK_LOSS_HINGE) && !bloom &&
-                    (optim->kind == SLK_OPT_ADAGRAD || optim->kind == SLK_OPT_SGD) && ctx->opt_user_bias_zero_hint;
-            a.nt = ctx->opt_nt;
-            // Round 6 (profiles/r06_mall_ab.jsonl): a minibatch whose records are as large as the Infinity Cache (2^20 x 256 B
-            // = 256 MB) cannot keep them there until the item pass reads them -- written with plain stores they only evict the
-            // item table, which the user pass re-reads twice per interaction.  Non-temporal record stores: C2 step -0.9 %
-            // (item pass 0.3165 -> 0.3122 ms), C5 shard -0.2 %; a minibatch of 65 536 (16 MB of records: they DO stay) +4 %, so
-            // only above "record_nt_min_bytes".
-            if (ctx->opt_record_nt_min_bytes > 0 && (int64_t)bm * RS * 4 >= ctx->opt_record_nt_min_bytes) a.nt |= 16;
-            // overlapped prep: the user pass is a grid-stride kernel whose workgroups hold their wave slots for the whole run; two
-            // of the eight per CU are left to the prep stream's kernels (measured, profiles/r03_a_*: 8 -> 6 costs the pass
-            // nothing by itself and gives the overlap 2 % more)
-            const int ugm = side && ctx->opt_user_grid_mult > 6 ? 6 : ctx->opt_user_grid_mult;
-            const unsigned ugrid = slk_grid_for(ctx, bm, gpb, ugm < occ_user ? ugm : occ_user);
-
-            if (expl && ctx->opt_explicit_fused) {
-                // the user pass forms score, loss and dL/dscore itself (one pair per interaction)
-                a.ratings = d_ratings + c0;
-                a.n_loss_partial = (int)ugrid;
-            } else if (expl) {
-                slk_prof_begin(ctx, SLK_K_SCORE, s);
-                hipLaunchKernelGGL(spass, dim3(ugrid), dim3(256), 0, s, a);
-                SLK_LAUNCH_CHECK(ctx, "k_score_pass");
-                const unsigned sgrid = slk_grid_for(ctx, bm, 256);
-                hipLaunchKernelGGL(k_explicit_loss, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p,
-                                   d_ratings + c0, (float *)ctx->gk.p, b0, bm, (int)loss, a.inv_b,
-                                   (double *)ctx->losspart.p);
-                SLK_LAUNCH_CHECK(ctx, "k_explicit_loss");
-                a.n_loss_partial = (int)sgrid;
-                slk_prof_end(ctx, s);
-            } else if (adaptive) {
-                slk_prof_begin(ctx, SLK_K_SCORE, s);
-                hipLaunchKernelGGL(spass, dim3(ugrid), dim3(256), 0, s, a);
-                SLK_LAUNCH_CHECK(ctx, "k_score_pass");
-                const unsigned sgrid = slk_grid_for(ctx, bm, 256);
-                hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p,
-                                   (float *)ctx->gk.p, b0, bm, nn, a.inv_b, (double *)ctx->losspart.p,
-                                   late ? (const uint32_t *)pb.ipay[0].p : (const uint32_t *)nullptr,
-                                   late ? (uint32_t *)ctx->extra[BL_LIVE].p : (uint32_t *)nullptr);
-                SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
-                a.n_loss_partial = (int)sgrid;
-                slk_prof_end(ctx, s);
-                if (late) {
-                    // this minibatch's live occurrences, sorted by item (biases; rows of a plain table)
-                    slk_prof_begin(ctx, SLK_K_PREP, s);
-                    const uint32_t nl = 2 * bm;
-                    hipLaunchKernelGGL(k_build_live_keys, dim3(slk_grid_for(ctx, nl, 256)), dim3(256), 0, s,
-                                       (const uint32_t *)ctx->extra[BL_LIVE].p, uit, nl, ibd, false,
-                                       (uint32_t *)ctx->extra[BL_LK0].p, (uint32_t *)ctx->extra[BL_LV0].p);
-                    SLK_LAUNCH_CHECK(ctx, "k_build_live_keys");
-                    if ((rc = slk_sort_pairs_u32_u32_in(ctx, ctx->extra[BL_LATE_SORT], (const uint32_t *)ctx->extra[BL_LK0].p,
-                                                     (uint32_t *)ctx->extra[BL_LK1].p,
-                                                     (const uint32_t *)ctx->extra[BL_LV0].p,
-                                                     (uint32_t *)ctx->extra[BL_LV1].p, nl, ibits + 1, s, true)))  // + the dead entries' bit
-                        return rc;
-                    slk_prof_end(ctx, s);
-                    a.ikey = (const uint32_t *)ctx->extra[BL_LK1].p;
-                    a.ipay = (const uint32_t *)ctx->extra[BL_LV1].p;
-                    a.imask = 0xffffffffu;
-                    a.ibegin = 0;
-                    a.iend = nl;
-                    // a.pad_item2 == ~0u: the dead entries' all-ones key is never updated
-                }
-            } else {
-                a.n_loss_partial = (int)ugrid;
-            }
-
-            if (!lflags_ready) {
-                // the flags are produced by the chunk's sorts, long before the previous chunk's passes are through: the GPU has
-                // work queued while the host waits for the read-back
-                if (pb.ev_lflags && pb.h_lflags_n) SLK_HIP(ctx, hipEventSynchronize(pb.ev_lflags));
-                lflags_ready = true;
-            }
-            const uint32_t mb_c = b0 / (uint32_t)bsz;
-            const bool have_flags = pb.h_lflags_n >= 2 * (size_t)n_mb_c;
-            const bool item_may_long = late || !ctx->opt_item_long_gate || !have_flags || pb.h_lflags[mb_c] != 0;
-            const bool user_may_long = !bloom && (!ctx->opt_item_long_gate || !have_flags || pb.h_lflags[n_mb_c + mb_c] != 0);
-
-            slk_prof_begin(ctx, SLK_K_USER_PASS, s);
-            const bool lat = upass_lat && (int64_t)bm <= ctx->opt_user_lat_max_batch;
-            // Option "user_grid_own_occ" (off): the grid of the form that is launched capped at THAT form's occupancy instead of the
-            // smallest of the four forms' -- measured in round 6 and not kept (slk_common.h)
-            // the single-occurrence fast path rides on the plain (bandwidth-bound) form only: a minibatch that takes the latency-bound
-            // or the long-run form leaves every item to the item pass
-            const bool sgl = sgl_on && upass_sgl && !user_may_long && !lat;
-            if (sgl) {
-                a.mflag = (const uint8_t *)pb.mflag.p;
-                a.msorted = (const uint8_t *)pb.msorted.p;
-                ++ctx->stat_single;
-            }
-            const pass_fn uform = sgl ? upass_sgl : (user_may_long ? (lat ? upass_lat_long : upass_long) : (lat ? upass_lat : upass));
-            unsigned ugrid_form = ugrid;
-            if (ctx->opt_user_grid_own_occ || sgl) {  // (the single-occurrence form holds more registers than the four whose smallest occupancy caps the others)
-                const int occ_form = slk_occupancy_of(ctx, uform);
-                ugrid_form = slk_grid_for(ctx, bm, gpb, ugm < occ_form ? ugm : occ_form);
-                if (!pre || (expl && ctx->opt_explicit_fused)) a.n_loss_partial = (int)ugrid_form;  // (the pass writes one loss partial per workgroup)
-            }
-            if (user_may_long) {
-                if (ctx->upart_gen >= 0x0ffffffeu) {  // the 28-bit stamp wraps: forget every old partial
-                    SLK_HIP(ctx, hipMemsetAsync(ctx->upart_meta.p, 0, ctx->upart_meta.cap, s));
-                    ctx->upart_gen = 0u;
-                }
-                ++ctx->upart_gen;
-                a.upart = (float *)ctx->extra[BL_UPART].p;
-                a.upart_meta = (uint32_t *)ctx->upart_meta.p;
-                a.upart_count = a.upart_meta + 4 * utiles;
-                a.upart_gen = ctx->upart_gen;
-                a.UPS = UPS;
-                SLK_HIP(ctx, hipMemsetAsync(a.upart_count, 0, 4, s));
-                hipLaunchKernelGGL(uform, dim3(ugrid_form), dim3(256), 0, s, a);
-                SLK_LAUNCH_CHECK(ctx, "k_user_pass<ULONG>");
-                ++ctx->stat_user_long;
-                hipLaunchKernelGGL(ustitch, dim3(slk_grid_for(ctx, ((size_t)bm + SLK_USER_TILE - 1) / SLK_USER_TILE, gpb)), dim3(256), 0, s, a);
-                SLK_LAUNCH_CHECK(ctx, "k_user_stitch");
-            } else {
-                hipLaunchKernelGGL(uform, dim3(ugrid_form), dim3(256), 0, s, a);
-                SLK_LAUNCH_CHECK(ctx, "k_user_pass");
-            }
-            slk_prof_end(ctx, s);
-            slk_prof_begin(ctx, SLK_K_ITEM_PASS, s);
-            if (!Hi) {
-                if ((rc = slk_launch_item_pass(ctx, sgl ? ipass_sgl : ipass, a, g, s, "k_item_pass", item_may_long))) return rc;
-            } else {
-                // item biases are indexed by the item id: plain occurrence list, bias only ...
-                if ((rc = slk_launch_item_pass(ctx, ipass_bias, a, g, s, "k_item_pass<BIAS>", item_may_long))) return rc;
-                // ... while every occurrence feeds the n_hash hashed rows of the compressed table
-                slk_pass_args r = a;
-                r.mb_loss_out = nullptr;
-                r.ikey = (const uint32_t *)pb.bik[1].p;
-                r.ipay = (const uint32_t *)pb.bip[1].p;
-                r.ibegin = a.ibegin * (uint32_t)Hi;
-                r.iend = a.iend * (uint32_t)Hi;
-                r.imask = (uint32_t)((1ull << icbits) - 1);
-                if (late) {
-                    // the live occurrences' hashed rows (the bias pass above has consumed LK1/LV1:
-                    // same stream, so the buffers can be reused)
-                    const uint32_t nlh = 2 * bm * (uint32_t)Hi;
-                    hipLaunchKernelGGL(k_build_live_keys, dim3(slk_grid_for(ctx, nlh, 256)), dim3(256), 0, s,
-                                       (const uint32_t *)ctx->extra[BL_LIVE].p, uit, 2 * bm, ibd, true,
-                                       (uint32_t *)ctx->extra[BL_LK0].p, (uint32_t *)ctx->extra[BL_LV0].p);
-                    SLK_LAUNCH_CHECK(ctx, "k_build_live_keys<hashed>");
-                    if ((rc = slk_sort_pairs_u32_u32_in(ctx, ctx->extra[BL_LATE_SORT], (const uint32_t *)ctx->extra[BL_LK0].p,
-                                                     (uint32_t *)ctx->extra[BL_LK1].p,
-                                                     (const uint32_t *)ctx->extra[BL_LV0].p,
-                                                     (uint32_t *)ctx->extra[BL_LV1].p, nlh, icbits + 1, s, true)))
-                        return rc;
-                    r.ikey = (const uint32_t *)ctx->extra[BL_LK1].p;
-                    r.ipay = (const uint32_t *)ctx->extra[BL_LV1].p;
-                    r.ibegin = 0;
-                    r.iend = nlh;
-                    r.imask = 0xffffffffu;
-                }
-                r.pad_item = tables->item_bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)tables->item_bloom->skip_row;
-                if ((rc = slk_launch_item_pass(ctx, ipass_rows, r, g, s, "k_item_pass<ROWS>"))) return rc;
-            }
-            if (Hu) {
-                // owner pass over the hashed USER rows: table slot 1 of the pass is remapped onto
-                // the user embedding table, records are the segment gradients parked by the user pass
-                slk_pass_args r = a;
-                r.mb_loss_out = nullptr;
-                r.P[1] = a.P[0];
-                r.S1[1] = a.S1[0];
-                r.S2[1] = a.S2[0];
-                r.snap = a.urec;
-                r.RS = RSU;
-                r.ikey = (const uint32_t *)pb.buk[1].p;
-                r.ipay = (const uint32_t *)pb.bup[1].p;
-                r.ibegin = b0 * (uint32_t)Hu;
-                r.iend = b1 * (uint32_t)Hu;
-                r.imask = (uint32_t)((1ull << ucbits) - 1);
-                r.pad_item = tables->user_bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)tables->user_bloom->skip_row;
-                r.pad_item2 = ubd.rows;  // sentinel of non-head positions
-                if ((rc = slk_launch_item_pass(ctx, rpass_rows, r, g, s, "k_item_pass<ROW,ROWS>"))) return rc;
-            }
-            slk_prof_end(ctx, s);
-
-            if (dense && (rc = slk_dense_sweeps(ctx, tables->d_param, optim, 15u, s))) return rc;
-            optim->step += 1;
-        }
-        return SLK_OK;
-    };
-
-    auto do_chunk = [&](size_t ck, slk_prep_bufs &pb) -> int {
-        if (!epoch_route) return do_passes(ck, pb);
-        const int64_t c0 = cb[ck];
-        const uint32_t nc = (uint32_t)(cb[ck + 1] - c0);
-        int rc = slk_epoch_run_chunk(ctx, tables, optim, pb, nc, bsz, ubits, ibits, (int)loss, NP, RS, (float *)ctx->snap.p,
-                                     (float *)ctx->extra[BL_GSN].p, d_mb_loss + mb_global, expl ? d_ratings + c0 : nullptr, s);
-        if (rc == SLK_EAGAIN_EPOCH) {  // cooperative launch refused: nothing ran; per-minibatch launches from here on
-            epoch_route = false;
-            if (dense && (rc = ensure_dense_buffers())) return rc;
-            return do_passes(ck, pb);
-        }
-        mb_global += (nc + bsz - 1) / bsz;
-        return rc;
-    };
-
-    // a chunk prepared ahead by slk_bilinear_prefetch: it must be THIS call's first chunk (its negatives are already drawn)
-    // (a call that draws nothing -- negatives handed in, explicit feedback -- cannot be confused with the prepared one: it drops
-    // the chunk instead of refusing; fit() of another model after one that left its loop by an exception, ADVICE r04)
-    if (!prefetch_only && ctx->pf.valid && (d_neg_in || expl)) ctx->pf.valid = false;
-    const bool have0 = !prefetch_only && ctx->pf.valid;
-    if (have0 && (!side || epoch_route || ctx->pf.users != (const void *)d_users || ctx->pf.items != (const void *)d_items ||
-                  ctx->pf.n != n || ctx->pf.bsz != bsz || ctx->pf.loss != (int)loss || ctx->pf.nn != nn || ctx->pf.nc0 != cb[1] || d_neg_in)) {
-        ctx->pf.valid = false;
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: a chunk was prepared ahead (slk_bilinear_prefetch) for another call; its "
-                                         "draws are consumed -- set the RNG state again");
     }
-    if (!prefetch_only) ctx->pf.valid = false;
-    if (prefetch_only) {
-        ctx->pf.valid = false;
-        if (!side || epoch_route || d_neg_in) return SLK_OK;  // such a call prepares in line: nothing to run ahead
-        if ((rc = slk_prep_stream_init(ctx))) return rc;
-        hipStream_t ps = ctx->prep_stream;
-        // the set the call before did NOT finish on: its last reader were the passes two chunks back (ev_done of that set)
-        const int set = ctx->last_pipe_set >= 0 ? (ctx->last_pipe_set ^ 1) : 0;
-        // What the prepared chunk waits for (it used to wait for everything the caller's stream held -- every pass of
-        // the epoch before -- and so ran BEHIND those passes, not beside them): the id arrays are complete when this call is made
-        // (the header says so; fit() has read the shuffle's RNG state back, which synchronises the lane that wrote them); buffer
-        // set `set` was last read by the passes two chunks back (ev_done); the sampler's and the sorts' scratch and, with
-        // "overlap_prep" 1, the earlier readers of pf_neg (the sorts of the running call's later chunks) live on the prep stream
-        // itself.  Only with "overlap_prep" 2 do sorts that read pf_neg run on the caller's stream: then, and only then, the
-        // new draw waits for that stream's tail.
-        //  That holds for a ctx whose last training call was a pipelined one.  After an IN-LINE call (one buffer
-        // set, "overlap_prep" 0 / 2: sampler, sorts and buffer set 0 were used on the caller's stream -- ctx->last_pipe_set < 0)
-        // the new draw waits for that stream's tail; after an in-line slk_sample_items it waits for that draw's own event.
-        if (ctx->opt_overlap_prep != 1 || ctx->opt_prefetch_wait || ctx->last_pipe_set < 0) {
-            SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));
-            SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
-        } else if (ctx->sampled_valid && ctx->ev_sampled) {
-            SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_sampled, 0));  // (recorded on the prep stream itself in the steady state: free)
+    return slk_sample_u32(ctx, c.tables->num_items, (int64_t)nneg, u32p(pb.neg32), c.neg_out ? c.neg_out + c0 * p.nn : nullptr, s);
+}
+
+// The single-occurrence flags of a chunk's item-sorted list: which occurrences are NOT the only one of their item in their
+// minibatch (ids only).  Behind the item sort of the chunk, on the same stream or one that waits for it.
+static int prep_single_flags(slk_ctx *ctx, const train_plan &p, const train_call &c, slk_prep_bufs &pb, size_t ck, hipStream_t s) {
+    const uint32_t nocc = chunk_len(p, c, ck) * (uint32_t)p.NP;
+    SLK_HIP(ctx, hipMemsetAsync(pb.mflag.p, 0, (size_t)nocc, s));
+    hipLaunchKernelGGL(k_item_multi_flags, dim3(slk_grid_for(ctx, nocc, 256)), dim3(256), 0, s, (const uint32_t *)pb.ikey[1].p,
+                       (const uint32_t *)pb.ipay[1].p, nocc, (uint32_t)p.bsz * (uint32_t)p.NP, (uint8_t *)pb.msorted.p, (uint8_t *)pb.mflag.p);
+    SLK_LAUNCH_CHECK(ctx, "k_item_multi_flags");
+    return SLK_OK;
+}
+
+static int prep_sort(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_run &run, size_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    int rc;
+    const int64_t c0 = chunk_begin(p, ck);
+    const uint32_t nc = chunk_len(p, c, ck), nocc = nc * (uint32_t)p.NP, bsz = (uint32_t)p.bsz;
+    const int64_t *cu = c.users + c0, *ci = c.items + c0;
+    const uint32_t *neg32 = run.neg_all ? run.neg_all + (size_t)c0 * p.nn : u32p(pb.neg32);
+    const int Hi = p.Hi, Hu = p.Hu;
+
+    // ---- prep: sort interactions by (minibatch, user), occurrences by (minibatch, item)
+    slk_prof_begin(ctx, SLK_K_PREP, s);
+    const unsigned mbbits = slk_bits_for((uint64_t)((nc - 1) / bsz));
+    uint32_t *const ukey = u32p(pb.ukey[1]);
+    const uint32_t *uit, *uk = nullptr;
+    uint32_t *const ukeys[2] = {u32p(pb.ukey[0]), ukey};
+    if (!p.pre) {
+        // (keys and the fat (positive, negative) payload are formed by the sort's first pass from the id arrays)
+        uint64_t *const uvals[2] = {(uint64_t *)pb.uval[0].p, (uint64_t *)pb.uval[1].p};
+        if ((rc = slk_sort_user_fat(ctx, cu, ci, neg32, nc, (size_t)bsz, p.ubits, mbbits, ukeys, uvals, s))) return rc;
+        uit = u32p(pb.uval[1]);  // little-endian (pos, neg) pairs
+    } else {
+        uint32_t *const uvals[2] = {u32p(pb.uval[0]), u32p(pb.uval[1])};
+        if ((rc = slk_sort_user_idx(ctx, cu, nc, (size_t)bsz, p.ubits, mbbits, ukeys, uvals, s))) return rc;
+        uk = u32p(pb.uval[1]);
+        hipLaunchKernelGGL(k_pack_items, dim3(slk_grid_for(ctx, nc, 256)), dim3(256), 0, s, uk, ci, neg32, nc, p.nn, u32p(pb.uit));
+        SLK_LAUNCH_CHECK(ctx, "k_pack_items");
+        uit = u32p(pb.uit);
+    }
+    if (p.late) {
+        hipLaunchKernelGGL(k_invert_perm, dim3(slk_grid_for(ctx, nc, 256)), dim3(256), 0, s, uk, nc, u32p(pb.ipay[0]));
+        SLK_LAUNCH_CHECK(ctx, "k_invert_perm");
+    } else {
+        uint32_t *const ikeys[2] = {u32p(pb.ikey[0]), u32p(pb.ikey[1])};
+        uint32_t *const ivals[2] = {u32p(pb.ipay[0]), u32p(pb.ipay[1])};
+        if ((rc = slk_sort_item_occ(ctx, uit, nocc, (size_t)bsz, p.NP, p.ibits, mbbits, ikeys, ivals, s))) return rc;
+        if (p.sgl_on && (rc = prep_single_flags(ctx, p, c, pb, ck, s))) return rc;
+    }
+    // which minibatches hold a LONG run (an item run that wholly covers a tile of the item pass, [0, n_mb); a user run that
+    // wholly covers a tile of the user pass, [n_mb, 2 n_mb)): ids only, so the answer is fetched once per chunk and the usual
+    // minibatch (none) gets the plain passes with no stitch kernel behind them
+    if (!run.epoch_route) {  // (the persistent route walks the runs itself; its fall-back takes the long forms, run_passes)
+        const uint32_t n_mb_c = (nc + bsz - 1) / bsz;
+        const unsigned gpb = 256u / (unsigned)p.g;
+        if ((rc = slk_ensure(ctx, pb.lflags, 2 * (size_t)n_mb_c * 4))) return rc;
+        SLK_HIP(ctx, hipMemsetAsync(pb.lflags.p, 0, 2 * (size_t)n_mb_c * 4, s));
+        if (!p.late) {
+            hipLaunchKernelGGL(k_item_long_flags, dim3(slk_grid_for(ctx, nocc / (4 * gpb) + n_mb_c, 256)), dim3(256), 0, s,
+                               (const uint32_t *)pb.ikey[1].p, nocc, bsz * (uint32_t)p.NP, 4u * gpb,
+                               (uint32_t)((1ull << p.ibits) - 1), 0xffffffffu, 0xffffffffu, (int *)pb.lflags.p);
+            SLK_LAUNCH_CHECK(ctx, "k_item_long_flags");
         }
-        SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[set], 0));
-        // The negatives of the WHOLE call in one draw (it is one contiguous draw however the call is chunked): the stream
-        // position behind them -- where the NEXT epoch's shuffle starts -- is then known an epoch ahead
-        // (slk_rng_get_state_sampled), and the training call itself draws nothing.  Calls of >= 2^30 draws keep drawing by chunk.
-        const bool all = nn > 0 && (uint64_t)n * (uint64_t)nn < ((uint64_t)1 << 30);
-        if (all) {
-            if ((rc = slk_ensure(ctx, ctx->pf_neg, (size_t)n * nn * 4))) return rc;
-            if ((rc = slk_sample_u32(ctx, tables->num_items, n * (int64_t)nn, (uint32_t *)ctx->pf_neg.p, nullptr, ps))) return rc;
-            neg_all = (const uint32_t *)ctx->pf_neg.p;
-        } else if ((rc = do_sample(0, ctx->pb[set], ps))) {
+        if (!p.bloom) {
+            hipLaunchKernelGGL(k_user_long_flags, dim3(slk_grid_for(ctx, nc / SLK_USER_TILE + n_mb_c, 256)), dim3(256), 0, s,
+                               (const uint32_t *)ukey, nc, bsz, (int *)pb.lflags.p + n_mb_c);
+            SLK_LAUNCH_CHECK(ctx, "k_user_long_flags");
+        }
+        if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)n_mb_c))) return rc;
+        SLK_HIP(ctx, hipMemcpyAsync(pb.h_lflags, pb.lflags.p, 2 * (size_t)n_mb_c * 4, hipMemcpyDeviceToHost, s));
+        if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
+        SLK_HIP(ctx, hipEventRecord(pb.ev_lflags, s));
+    } else {
+        pb.h_lflags_n = 0;  // no flags for this chunk: every pass of a fall-back takes the partial-writing form
+    }
+    if (Hi && !p.late) {
+        hipLaunchKernelGGL(k_build_item_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nocc * Hi, 256)), dim3(256), 0, s,
+                           uit, nocc, p.NP, bsz, p.icbits, p.ibd, u32p(pb.bik[0]), u32p(pb.bip[0]));
+        SLK_LAUNCH_CHECK(ctx, "k_build_item_bloom_keys");
+        if ((rc = slk_sort_pairs_u32_u32(ctx, u32p(pb.bik[0]), u32p(pb.bik[1]), u32p(pb.bip[0]), u32p(pb.bip[1]), (size_t)nocc * Hi,
+                                         p.icbits + mbbits, s, true)))
             return rc;
+    }
+    if (Hu) {
+        hipLaunchKernelGGL(k_build_user_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nc * Hu, 256)), dim3(256), 0, s,
+                           (const uint32_t *)ukey, (uint32_t)((1ull << p.ubits) - 1), nc, bsz, p.ucbits, p.ubd,
+                           u32p(pb.buk[0]), u32p(pb.bup[0]));
+        SLK_LAUNCH_CHECK(ctx, "k_build_user_bloom_keys");
+        if ((rc = slk_sort_pairs_u32_u32(ctx, u32p(pb.buk[0]), u32p(pb.buk[1]), u32p(pb.bup[0]), u32p(pb.bup[1]), (size_t)nc * Hu,
+                                         p.ucbits + mbbits, s, true)))
+            return rc;
+    }
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+// ---- the minibatches of one prepared chunk, in order, on the caller's stream
+struct minibatch {
+    uint32_t b0, b1, bm;  // chunk-local interactions [b0, b1)
+    slk_pass_args a;
+    int ugm;              // workgroups per CU of the user pass's grid ...
+    unsigned ugrid;       // ... and that grid, capped at the smallest occupancy of the four forms
+    bool item_may_long, user_may_long;  // the chunk's long-run flags (prep_sort) do not rule a long run out
+    bool sgl;             // the user pass also updates the items that occur once in the minibatch (the item pass skips them)
+};
+
+// What every pass of chunk `ck` is handed, whichever its minibatch.
+static void chunk_pass_args(slk_ctx *ctx, const train_plan &p, const train_call &c, size_t ck, const slk_prep_bufs &pb, slk_pass_args *args) {
+    slk_pass_args &a = *args;
+    const slk_tables *tables = c.tables;
+    const slk_optim *optim = c.optim;
+    memset(&a, 0, sizeof(a));
+    for (int t = 0; t < 4; ++t) {
+        a.P[t] = tables->d_param[t];
+        a.S1[t] = p.dense ? f32p(ctx->dgrad[t]) : optim->d_state1[t];
+        a.S2[t] = optim->d_state2[t];
+    }
+    if (p.shadowed) {
+        a.P[3] = f32p(ctx->bias_shadow);
+        a.S1[3] = f32p(ctx->bias_shadow) + 1;
+        a.bsh3 = 1u;
+    }
+    if (p.pingpong) {
+        a.P0alt = f32p(ctx->pp_alt);
+        a.uflag = (uint8_t *)ctx->pp_flags.p;
+    }
+    a.D = p.D;
+    a.NP = p.NP;
+    a.ukey = u32p(pb.ukey[1]);
+    a.umask = (uint32_t)((1ull << p.ubits) - 1);
+    a.uit = p.pre ? u32p(pb.uit) : u32p(pb.uval[1]);
+    a.uk = p.pre ? u32p(pb.uval[1]) : nullptr;
+    a.gk = f32p(ctx->gk);
+    a.sk = f32p(ctx->sk);
+    a.snap = f32p(ctx->snap);
+    a.RS = p.RS;
+    a.gsn = f32p(ctx->extra[BL_GSN]);
+    a.ikey = u32p(pb.ikey[1]);
+    a.imask = (uint32_t)((1ull << p.ibits) - 1);
+    a.ipay = u32p(pb.ipay[1]);
+    a.loss_partial = (double *)ctx->losspart.p;
+    a.loss_kind = c.loss;
+    a.pad_item = a.pad_item2 = 0xffffffffu;
+    a.ub = p.ubd;
+    a.ib = p.ibd;
+    a.urec = f32p(ctx->extra[BL_UREC]);
+    a.RSU = p.RSU;
+    // user biases the caller vouches are all zero, a loss whose user-bias gradient is exactly zero, an update for which a
+    // zero gradient is an exact no-op: nothing of the table is read or written by the pair-mode user pass
+    a.ubz = (tables->flags & SLK_TABLES_USER_BIAS_ZERO) && (c.loss == SLK_LOSS_BPR || c.loss == SLK_LOSS_HINGE) && !p.bloom &&
+            (optim->kind == SLK_OPT_ADAGRAD || optim->kind == SLK_OPT_SGD) && ctx->opt_user_bias_zero_hint;
+    a.nt = ctx->opt_nt;
+    if (p.fused) a.ratings = c.ratings + chunk_begin(p, ck);  // the user pass forms score, loss and dL/dscore itself (one pair per interaction)
+}
+
+// this minibatch's live occurrences (k_adaptive_select), as item ids or as their hashed rows, sorted: BL_LK1 / BL_LV1
+static int sort_live_list(slk_ctx *ctx, const train_plan &p, const minibatch &mb, bool hashed, hipStream_t s) {
+    const uint32_t n = 2 * mb.bm * (hashed ? (uint32_t)p.Hi : 1u);
+    hipLaunchKernelGGL(k_build_live_keys, dim3(slk_grid_for(ctx, n, 256)), dim3(256), 0, s, (const uint32_t *)ctx->extra[BL_LIVE].p,
+                       mb.a.uit, 2 * mb.bm, p.ibd, hashed, u32p(ctx->extra[BL_LK0]), u32p(ctx->extra[BL_LV0]));
+    SLK_LAUNCH_CHECK(ctx, hashed ? "k_build_live_keys<hashed>" : "k_build_live_keys");
+    return slk_sort_pairs_u32_u32_in(ctx, ctx->extra[BL_LATE_SORT], u32p(ctx->extra[BL_LK0]), u32p(ctx->extra[BL_LK1]),
+                                     u32p(ctx->extra[BL_LV0]), u32p(ctx->extra[BL_LV1]), n, (hashed ? p.icbits : p.ibits) + 1, s,
+                                     true);  // + the dead entries' bit
+}
+
+// dL/dscore where the user pass does not form it itself: explicit feedback (staged), adaptive hinge and its late live list
+static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, size_t ck, const slk_prep_bufs &pb, minibatch &mb, hipStream_t s) {
+    slk_pass_args &a = mb.a;
+    int rc;
+    a.n_loss_partial = (int)mb.ugrid;
+    if (!p.pre || p.fused) return SLK_OK;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    hipLaunchKernelGGL(k.spass, dim3(mb.ugrid), dim3(256), 0, s, a);
+    SLK_LAUNCH_CHECK(ctx, "k_score_pass");
+    const unsigned sgrid = slk_grid_for(ctx, mb.bm, 256);
+    if (p.expl) {
+        hipLaunchKernelGGL(k_explicit_loss, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, c.ratings + chunk_begin(p, ck),
+                           f32p(ctx->gk), mb.b0, mb.bm, (int)c.loss, a.inv_b, (double *)ctx->losspart.p);
+        SLK_LAUNCH_CHECK(ctx, "k_explicit_loss");
+    } else {
+        hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, f32p(ctx->gk), mb.b0, mb.bm,
+                           p.nn, a.inv_b, (double *)ctx->losspart.p, p.late ? (const uint32_t *)pb.ipay[0].p : (const uint32_t *)nullptr,
+                           p.late ? u32p(ctx->extra[BL_LIVE]) : (uint32_t *)nullptr);
+        SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
+    }
+    a.n_loss_partial = (int)sgrid;
+    slk_prof_end(ctx, s);
+    if (p.late) {
+        // this minibatch's live occurrences, sorted by item (biases; rows of a plain table)
+        slk_prof_begin(ctx, SLK_K_PREP, s);
+        if ((rc = sort_live_list(ctx, p, mb, false, s))) return rc;
+        slk_prof_end(ctx, s);
+        a.ikey = u32p(ctx->extra[BL_LK1]);
+        a.ipay = u32p(ctx->extra[BL_LV1]);
+        a.imask = 0xffffffffu;
+        a.ibegin = 0;
+        a.iend = 2 * mb.bm;
+        // a.pad_item2 == ~0u: the dead entries' all-ones key is never updated
+    }
+    return SLK_OK;
+}
+
+// The user pass in the form this minibatch takes
+static int user_stage(slk_ctx *ctx, const train_plan &p, const train_kernels &k, const slk_prep_bufs &pb, minibatch &mb, hipStream_t s) {
+    slk_pass_args &a = mb.a;
+    slk_prof_begin(ctx, SLK_K_USER_PASS, s);
+    const bool lat = k.upass_lat && (int64_t)mb.bm <= ctx->opt_user_lat_max_batch;
+    // the single-occurrence fast path rides on the plain (bandwidth-bound) form only: a minibatch that takes the latency-bound
+    // or the long-run form leaves every item to the item pass
+    const bool sgl = mb.sgl = p.sgl_on && k.upass_sgl && !mb.user_may_long && !lat;
+    if (sgl) {
+        a.mflag = (const uint8_t *)pb.mflag.p;
+        a.msorted = (const uint8_t *)pb.msorted.p;
+        ++ctx->stat_single;
+    }
+    const pass_fn uform = sgl ? k.upass_sgl : (mb.user_may_long ? (lat ? k.upass_lat_long : k.upass_long) : (lat ? k.upass_lat : k.upass));
+    unsigned ugrid_form = mb.ugrid;
+    // Option "user_grid_own_occ" (off): the grid of the form that is launched capped at THAT form's occupancy instead of the
+    // smallest of the four forms' -- measured in round 6 and not kept (slk_common.h); the single-occurrence form always is
+    if (ctx->opt_user_grid_own_occ || sgl) {
+        const int occ_form = sgl ? k.occ_sgl : slk_occupancy_of(ctx, uform);
+        ugrid_form = slk_grid_for(ctx, mb.bm, k.gpb, mb.ugm < occ_form ? mb.ugm : occ_form);
+        if (!p.pre || p.fused) a.n_loss_partial = (int)ugrid_form;  // (the pass writes one loss partial per workgroup)
+    }
+    if (mb.user_may_long) {
+        if (ctx->upart_gen >= 0x0ffffffeu) {  // the 28-bit stamp wraps: forget every old partial
+            SLK_HIP(ctx, hipMemsetAsync(ctx->upart_meta.p, 0, ctx->upart_meta.cap, s));
+            ctx->upart_gen = 0u;
         }
-        if (ctx->opt_overlap_prep == 1 && (rc = do_sort(0, ctx->pb[set], ps))) return rc;
-        SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[set], ps));
-        ctx->pf.all = all;
-        ctx->pf.valid = true;
-        ctx->pf.set = set;
-        ctx->pf.users = d_users;
-        ctx->pf.items = d_items;
-        ctx->pf.n = n;
-        ctx->pf.bsz = bsz;
-        ctx->pf.nc0 = cb[1];
-        ctx->pf.loss = (int)loss;
-        ctx->pf.nn = nn;
-        return SLK_OK;
+        ++ctx->upart_gen;
+        a.upart = f32p(ctx->extra[BL_UPART]);
+        a.upart_meta = u32p(ctx->upart_meta);
+        a.upart_count = a.upart_meta + 4 * p.utiles;
+        a.upart_gen = ctx->upart_gen;
+        a.UPS = p.UPS;
+        SLK_HIP(ctx, hipMemsetAsync(a.upart_count, 0, 4, s));
+        hipLaunchKernelGGL(uform, dim3(ugrid_form), dim3(256), 0, s, a);
+        SLK_LAUNCH_CHECK(ctx, "k_user_pass<ULONG>");
+        ++ctx->stat_user_long;
+        hipLaunchKernelGGL(k.ustitch, dim3(slk_grid_for(ctx, ((size_t)mb.bm + SLK_USER_TILE - 1) / SLK_USER_TILE, k.gpb)), dim3(256), 0, s, a);
+        SLK_LAUNCH_CHECK(ctx, "k_user_stitch");
+    } else {
+        hipLaunchKernelGGL(uform, dim3(ugrid_form), dim3(256), 0, s, a);
+        SLK_LAUNCH_CHECK(ctx, "k_user_pass");
     }
-    if (nsets == 1) {
-        // one chunk: everything in order on the caller's stream
-        if ((rc = do_sample(0, ctx->pb[0], s))) return rc;
-        if ((rc = do_sort(0, ctx->pb[0], s))) return rc;
-        if ((rc = do_chunk(0, ctx->pb[0]))) return rc;
-        ctx->last_stream = s;
-        ctx->last_pipe_set = -1;
-        return SLK_OK;
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+// The row-owner passes over the item side: plain tables in one pass; a compressed item table as a bias pass over the plain
+// occurrence list and a row pass over the hashed one; a compressed user table's rows behind them
+static int item_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, const slk_prep_bufs &pb, minibatch &mb, hipStream_t s) {
+    slk_pass_args &a = mb.a;
+    const int Hi = p.Hi, Hu = p.Hu, g = p.g;
+    int rc;
+    slk_prof_begin(ctx, SLK_K_ITEM_PASS, s);
+    if (!Hi) {
+        if ((rc = slk_launch_item_pass(ctx, mb.sgl ? k.ipass_sgl : k.ipass, a, g, s, "k_item_pass", mb.item_may_long))) return rc;
+    } else {
+        // item biases are indexed by the item id: plain occurrence list, bias only ...
+        if ((rc = slk_launch_item_pass(ctx, k.ipass_bias, a, g, s, "k_item_pass<BIAS>", mb.item_may_long))) return rc;
+        // ... while every occurrence feeds the n_hash hashed rows of the compressed table
+        slk_pass_args r = a;
+        r.mb_loss_out = nullptr;
+        r.ikey = u32p(pb.bik[1]);
+        r.ipay = u32p(pb.bip[1]);
+        r.ibegin = a.ibegin * (uint32_t)Hi;
+        r.iend = a.iend * (uint32_t)Hi;
+        r.imask = (uint32_t)((1ull << p.icbits) - 1);
+        if (p.late) {
+            // the live occurrences' hashed rows (the bias pass above has consumed LK1/LV1:
+            // same stream, so the buffers can be reused)
+            if ((rc = sort_live_list(ctx, p, mb, true, s))) return rc;
+            r.ikey = u32p(ctx->extra[BL_LK1]);
+            r.ipay = u32p(ctx->extra[BL_LV1]);
+            r.ibegin = 0;
+            r.iend = 2 * mb.bm * (uint32_t)Hi;
+            r.imask = 0xffffffffu;
+        }
+        r.pad_item = c.tables->item_bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)c.tables->item_bloom->skip_row;
+        if ((rc = slk_launch_item_pass(ctx, k.ipass_rows, r, g, s, "k_item_pass<ROWS>"))) return rc;
     }
-    // pipeline: prep(c + 1) is enqueued before passes(c) -- on ctx->prep_stream, beside them (`side`), or on the caller's own
-    // stream, ahead of them.
+    if (Hu) {
+        // owner pass over the hashed USER rows: table slot 1 of the pass is remapped onto
+        // the user embedding table, records are the segment gradients parked by the user pass
+        slk_pass_args r = a;
+        r.mb_loss_out = nullptr;
+        r.P[1] = a.P[0];
+        r.S1[1] = a.S1[0];
+        r.S2[1] = a.S2[0];
+        r.snap = a.urec;
+        r.RS = p.RSU;
+        r.ikey = u32p(pb.buk[1]);
+        r.ipay = u32p(pb.bup[1]);
+        r.ibegin = mb.b0 * (uint32_t)Hu;
+        r.iend = mb.b1 * (uint32_t)Hu;
+        r.imask = (uint32_t)((1ull << p.ucbits) - 1);
+        r.pad_item = c.tables->user_bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)c.tables->user_bloom->skip_row;
+        r.pad_item2 = p.ubd.rows;  // sentinel of non-head positions
+        if ((rc = slk_launch_item_pass(ctx, k.rpass_rows, r, g, s, "k_item_pass<ROW,ROWS>"))) return rc;
+    }
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+static int run_passes(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, train_run &run, size_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    int rc;
+    const uint32_t nc = chunk_len(p, c, ck), bsz = (uint32_t)p.bsz;
+    const uint32_t n_mb_c = (nc + bsz - 1) / bsz;
+    slk_pass_args chunk_args;
+    chunk_pass_args(ctx, p, c, ck, pb, &chunk_args);
+    // overlapped prep: the user pass is a grid-stride kernel whose workgroups hold their wave slots for the whole run; two
+    // of the eight per CU are left to the prep stream's kernels (measured, profiles/r03_a_*: 8 -> 6 costs the pass
+    // nothing by itself and gives the overlap 2 % more)
+    const int ugm = p.side && ctx->opt_user_grid_mult > 6 ? 6 : ctx->opt_user_grid_mult;
+    minibatch mb;
+    mb.ugm = ugm;
+    for (uint32_t b0 = 0; b0 < nc; b0 += bsz, ++run.mb_global) {
+        const uint32_t b1 = (nc - b0 < bsz) ? nc : b0 + bsz, bm = b1 - b0;
+        mb.b0 = b0, mb.b1 = b1, mb.bm = bm;
+        slk_pass_args &a = mb.a = chunk_args;
+        a.begin = b0;
+        a.end = b1;
+        a.ibegin = b0 * (uint32_t)p.NP;
+        a.iend = b1 * (uint32_t)p.NP;
+        a.inv_b = 1.0f / (float)bm;
+        a.mb_loss_out = c.mb_loss + run.mb_global;
+        slk_set_opt_coeffs(a, c.optim);
+        // Round 6 (profiles/r06_mall_ab.jsonl): a minibatch whose records are as large as the Infinity Cache (2^20 x 256 B
+        // = 256 MB) cannot keep them there until the item pass reads them -- written with plain stores they only evict the
+        // item table, which the user pass re-reads twice per interaction.  Non-temporal record stores: C2 step -0.9 %
+        // (item pass 0.3165 -> 0.3122 ms), C5 shard -0.2 %; a minibatch of 65 536 (16 MB of records: they DO stay) +4 %, so
+        // only above "record_nt_min_bytes".
+        if (ctx->opt_record_nt_min_bytes > 0 && (int64_t)bm * p.RS * 4 >= ctx->opt_record_nt_min_bytes) a.nt |= 16;
+        mb.ugrid = slk_grid_for(ctx, bm, k.gpb, ugm < k.occ_user ? ugm : k.occ_user);
+        if ((rc = score_stage(ctx, p, c, k, ck, pb, mb, s))) return rc;
+
+        // the chunk's long-run flags (prep_sort): ONE host wait per chunk, before the first user pass.  The flags are produced by
+        // the chunk's sorts, long before the previous chunk's passes are through: the GPU has work queued while the host waits
+        // for the read-back
+        if (b0 == 0 && pb.ev_lflags && pb.h_lflags_n) SLK_HIP(ctx, hipEventSynchronize(pb.ev_lflags));
+        const uint32_t mb_c = b0 / bsz;
+        const bool have_flags = pb.h_lflags_n >= 2 * (size_t)n_mb_c;
+        mb.item_may_long = p.late || !ctx->opt_item_long_gate || !have_flags || pb.h_lflags[mb_c] != 0;
+        mb.user_may_long = !p.bloom && (!ctx->opt_item_long_gate || !have_flags || pb.h_lflags[n_mb_c + mb_c] != 0);
+
+        if ((rc = user_stage(ctx, p, k, pb, mb, s))) return rc;
+        if ((rc = item_stage(ctx, p, c, k, pb, mb, s))) return rc;
+        if (p.dense && (rc = slk_dense_sweeps(ctx, c.tables->d_param, c.optim, 15u, s))) return rc;
+        c.optim->step += 1;
+    }
+    return SLK_OK;
+}
+
+static int run_chunk(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, train_run &run, size_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    if (!run.epoch_route) return run_passes(ctx, p, c, k, run, ck, pb, s);
+    const int64_t c0 = chunk_begin(p, ck);
+    const uint32_t nc = chunk_len(p, c, ck);
+    int rc = slk_epoch_run_chunk(ctx, c.tables, c.optim, pb, nc, p.bsz, p.ubits, p.ibits, (int)c.loss, p.NP, p.RS, f32p(ctx->snap),
+                                 f32p(ctx->extra[BL_GSN]), c.mb_loss + run.mb_global, p.expl ? c.ratings + c0 : nullptr, s);
+    if (rc == SLK_EAGAIN_EPOCH) {  // cooperative launch refused: nothing ran; per-minibatch launches from here on
+        run.epoch_route = false;
+        if (p.dense && (rc = ensure_dense_buffers(ctx, p, s))) return rc;
+        return run_passes(ctx, p, c, k, run, ck, pb, s);
+    }
+    run.mb_global += (nc + p.bsz - 1) / p.bsz;
+    return rc;
+}
+
+// slk_bilinear_prefetch: the first chunk of the call these arguments describe, on the prep stream, and the record of it (ctx->pf)
+static int prefetch_first_chunk(slk_ctx *ctx, const train_plan &p, const train_call &c, train_run &run) {
+    int rc;
+    hipStream_t s = c.s;
+    ctx->pf.valid = false;
+    if (!p.side || run.epoch_route || c.neg_in) return SLK_OK;  // such a call prepares in line: nothing to run ahead
+    if ((rc = slk_prep_stream_init(ctx))) return rc;
+    hipStream_t ps = ctx->prep_stream;
+    // the set the call before did NOT finish on: its last reader were the passes two chunks back (ev_done of that set)
+    const int set = ctx->last_pipe_set >= 0 ? (ctx->last_pipe_set ^ 1) : 0;
+    // What the prepared chunk waits for (it used to wait for everything the caller's stream held -- every pass of
+    // the epoch before -- and so ran BEHIND those passes, not beside them): the id arrays are complete when this call is made
+    // (the header says so; fit() has read the shuffle's RNG state back, which synchronises the lane that wrote them); buffer
+    // set `set` was last read by the passes two chunks back (ev_done); the sampler's and the sorts' scratch and, with
+    // "overlap_prep" 1, the earlier readers of pf_neg (the sorts of the running call's later chunks) live on the prep stream
+    // itself.  Only with "overlap_prep" 2 do sorts that read pf_neg run on the caller's stream: then, and only then, the
+    // new draw waits for that stream's tail.
+    //  That holds for a ctx whose last training call was a pipelined one.  After an IN-LINE call (one buffer
+    // set, "overlap_prep" 0 / 2: sampler, sorts and buffer set 0 were used on the caller's stream -- ctx->last_pipe_set < 0)
+    // the new draw waits for that stream's tail; after an in-line slk_sample_items it waits for that draw's own event.
+    if (ctx->opt_overlap_prep != 1 || ctx->opt_prefetch_wait || ctx->last_pipe_set < 0) {
+        SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));
+        SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
+    } else if (ctx->sampled_valid && ctx->ev_sampled) {
+        SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_sampled, 0));  // (recorded on the prep stream itself in the steady state: free)
+    }
+    SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[set], 0));
+    // The negatives of the WHOLE call in one draw: the stream position behind them -- where the NEXT epoch's shuffle starts --
+    // is then known an epoch ahead (slk_rng_get_state_sampled), and the training call itself draws nothing.
+    if (p.one_draw) {
+        if ((rc = slk_ensure(ctx, ctx->pf_neg, (size_t)c.n * p.nn * 4))) return rc;
+        if ((rc = slk_sample_u32(ctx, c.tables->num_items, c.n * (int64_t)p.nn, u32p(ctx->pf_neg), nullptr, ps))) return rc;
+        run.neg_all = u32p(ctx->pf_neg);
+    } else if ((rc = prep_sample(ctx, p, c, run, 0, ctx->pb[set], ps))) {
+        return rc;
+    }
+    if (ctx->opt_overlap_prep == 1 && (rc = prep_sort(ctx, p, c, run, 0, ctx->pb[set], ps))) return rc;
+    SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[set], ps));
+    ctx->pf = {true, set, c.users, c.items, c.n, p.bsz, (int64_t)p.nc_max, (int)c.loss, p.nn, p.one_draw, p.sgl_on};
+    return SLK_OK;
+}
+
+// one chunk: everything in order on the caller's stream
+static int run_inline(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, train_run &run) {
+    int rc;
+    if ((rc = prep_sample(ctx, p, c, run, 0, ctx->pb[0], c.s))) return rc;
+    if ((rc = prep_sort(ctx, p, c, run, 0, ctx->pb[0], c.s))) return rc;
+    if ((rc = run_chunk(ctx, p, c, k, run, 0, ctx->pb[0], c.s))) return rc;
+    ctx->last_stream = c.s;
+    ctx->last_pipe_set = -1;
+    return SLK_OK;
+}
+
+// pipeline: prep(c + 1) is enqueued before passes(c) -- on ctx->prep_stream, beside them (`side`), or on the caller's own
+// stream, ahead of them.  `have0`: chunk 0 was prepared ahead by slk_bilinear_prefetch (ctx->pf).
+static int run_pipelined(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, train_run &run, bool have0) {
+    int rc;
+    hipStream_t s = c.s;
+    const bool side = p.side;
     // overlap_prep = 1: negatives and sorts; = 2: only the negatives (the generator is ALU-bound and
     // shares the chip with the HBM-bound passes; the sorts stay in line on the caller's stream)
     const bool sort_ahead = !side || ctx->opt_overlap_prep == 1;
@@ -1854,30 +1920,35 @@ static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim
     }
     int set = have0 ? ctx->pf.set : 0;
     if (have0) ++ctx->stat_prefetched;
-    if (have0 && ctx->pf.all) neg_all = (const uint32_t *)ctx->pf_neg.p;
+    if (have0 && ctx->pf.all) run.neg_all = u32p(ctx->pf_neg);
+    // A chunk prepared ahead of slk_user_pingpong_begin was sorted without the single-occurrence flags this call reads: they
+    // are made below, behind the chunk's sorts.  (The opposite mismatch needs nothing: the flags are simply not read.)
+    const bool flags0 = have0 && sort_ahead && p.sgl_on && !ctx->pf.sgl_on;
     if (!have0) {
-        // The negatives of the WHOLE call in ONE draw (it is one contiguous draw however the call is chunked -- what
-        // slk_bilinear_prefetch does for fit()'s epochs): the generator's jump-ahead, ~130 us whatever the draw's length, is
-        // paid once per call instead of once per chunk (round 6: 0.0135 -> 0.0065 ms per C2 step at 20 minibatches per call).
-        // Calls of >= 2^30 draws and calls that are handed their negatives keep drawing / converting by chunk.
-        if (!d_neg_in && nn > 0 && (uint64_t)n * (uint64_t)nn < ((uint64_t)1 << 30)) {
-            if ((rc = slk_ensure(ctx, ctx->call_neg, (size_t)n * nn * 4))) return rc;
-            if ((rc = slk_sample_u32(ctx, tables->num_items, n * (int64_t)nn, (uint32_t *)ctx->call_neg.p, d_neg_out, ps))) return rc;
-            neg_all = (const uint32_t *)ctx->call_neg.p;
-        } else if ((rc = do_sample(0, ctx->pb[set], ps))) {
+        if (p.one_draw) {  // what slk_bilinear_prefetch does for fit()'s epochs
+            if ((rc = slk_ensure(ctx, ctx->call_neg, (size_t)c.n * p.nn * 4))) return rc;
+            if ((rc = slk_sample_u32(ctx, c.tables->num_items, c.n * (int64_t)p.nn, u32p(ctx->call_neg), c.neg_out, ps))) return rc;
+            run.neg_all = u32p(ctx->call_neg);
+        } else if ((rc = prep_sample(ctx, p, c, run, 0, ctx->pb[set], ps))) {
             return rc;
         }
-        if (sort_ahead && (rc = do_sort(0, ctx->pb[set], ps))) return rc;
+        if (sort_ahead && (rc = prep_sort(ctx, p, c, run, 0, ctx->pb[set], ps))) return rc;
         if (side) SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[set], ps));
     }
-    for (size_t ck = 0; ck < n_chunks; ++ck, set ^= 1) {
+    for (size_t ck = 0; ck < p.n_chunks; ++ck, set ^= 1) {
         if (side) SLK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_prep[set], 0));
-        if (ck == 0 && have0 && neg_all && d_neg_out) {  // the caller wants the draws: they were made ahead, as uint32
-            hipLaunchKernelGGL(k_u32_to_i64, dim3(slk_grid_for(ctx, (size_t)n * nn, 256)), dim3(256), 0, s, neg_all, d_neg_out, (size_t)n * nn);
+        if (ck == 0 && flags0) {
+            slk_prof_begin(ctx, SLK_K_PREP, s);
+            if ((rc = prep_single_flags(ctx, p, c, ctx->pb[set], 0, s))) return rc;
+            slk_prof_end(ctx, s);
+        }
+        if (ck == 0 && have0 && run.neg_all && c.neg_out) {  // the caller wants the draws: they were made ahead, as uint32
+            const size_t nneg = (size_t)c.n * p.nn;
+            hipLaunchKernelGGL(k_u32_to_i64, dim3(slk_grid_for(ctx, nneg, 256)), dim3(256), 0, s, run.neg_all, c.neg_out, nneg);
             SLK_LAUNCH_CHECK(ctx, "k_u32_to_i64");
         }
-        if (!sort_ahead && (rc = do_sort(ck, ctx->pb[set], s))) return rc;
-        if (ck + 1 < n_chunks) {
+        if (!sort_ahead && (rc = prep_sort(ctx, p, c, run, ck, ctx->pb[set], s))) return rc;
+        if (ck + 1 < p.n_chunks) {
             // the other buffer set was last read by the passes of the previous chunk (with a chunk prepared ahead: by the last
             // passes of the call before this one)
             if (side && (ck > 0 || have0)) SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[set ^ 1], 0));
@@ -1888,24 +1959,51 @@ static int bilinear_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim
                 SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));
                 SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
             }
-            if ((rc = do_sample(ck + 1, ctx->pb[set ^ 1], ps))) return rc;
-            if (sort_ahead && (rc = do_sort(ck + 1, ctx->pb[set ^ 1], ps))) return rc;
+            if ((rc = prep_sample(ctx, p, c, run, ck + 1, ctx->pb[set ^ 1], ps))) return rc;
+            if (sort_ahead && (rc = prep_sort(ctx, p, c, run, ck + 1, ctx->pb[set ^ 1], ps))) return rc;
             if (side) {
                 SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[set ^ 1], ps));
                 ++ctx->stat_overlapped;
             }
         }
-        if ((rc = do_chunk(ck, ctx->pb[set]))) return rc;
+        if ((rc = run_chunk(ctx, p, c, k, run, ck, ctx->pb[set], s))) return rc;
         if (side) SLK_HIP(ctx, hipEventRecord(ctx->ev_done[set], s));
     }
-    if (!side) {  // everything ran on the caller's stream: in-line semantics for what follows (slk_bilinear_prefetch)
-        ctx->last_pipe_set = -1;
-        ctx->last_stream = s;
-        return SLK_OK;
-    }
-    ctx->last_pipe_set = set ^ 1;  // (the loop's last increment undone: the set of the last chunk)
+    // not `side`: everything ran on the caller's stream -- in-line semantics for what follows (slk_bilinear_prefetch); else the
+    // set of the last chunk (the loop's last increment undone)
+    ctx->last_pipe_set = side ? (set ^ 1) : -1;
     ctx->last_stream = s;  // every prep is ordered before the tail of the caller's stream
     return SLK_OK;
+}
+
+static int run_training(slk_ctx *ctx, const train_call &c) {
+    if (!ctx) return SLK_EINVAL;
+    train_plan p;
+    int rc;
+    if ((rc = plan_training(ctx, c, &p))) return rc;
+    if (p.n_chunks == 0) return SLK_OK;
+    const bool training = c.mode == train_call::TRAIN;
+    if (p.shadowed && training) ++ctx->stat_shadowed;
+    if (p.pingpong && training) ++ctx->stat_pingpong;
+    if ((rc = ensure_scratch(ctx, p, c.s))) return rc;
+    if (c.mode == train_call::RESERVE) return reserve_extras(ctx, p, c);
+    train_kernels k;
+    pick_kernels(ctx, p, c.optim, &k);
+    train_run run = {nullptr, 0, p.epoch_route};
+    if (!training) return prefetch_first_chunk(ctx, p, c, run);
+
+    // a chunk prepared ahead by slk_bilinear_prefetch: it must be THIS call's first chunk (its negatives are already drawn)
+    // (a call that draws nothing -- negatives handed in, explicit feedback -- cannot be confused with the prepared one: it drops
+    // the chunk instead of refusing; fit() of another model after one that left its loop by an exception, ADVICE r04)
+    if (ctx->pf.valid && (c.neg_in || p.expl)) ctx->pf.valid = false;
+    const bool have0 = ctx->pf.valid;
+    ctx->pf.valid = false;
+    if (have0 && (!p.side || p.epoch_route || ctx->pf.users != (const void *)c.users || ctx->pf.items != (const void *)c.items ||
+                  ctx->pf.n != c.n || ctx->pf.bsz != p.bsz || ctx->pf.loss != (int)c.loss || ctx->pf.nn != p.nn ||
+                  ctx->pf.nc0 != (int64_t)p.nc_max || c.neg_in))
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: a chunk was prepared ahead (slk_bilinear_prefetch) for another call; its "
+                                         "draws are consumed -- set the RNG state again");
+    return p.nsets == 1 ? run_inline(ctx, p, c, k, run) : run_pipelined(ctx, p, c, k, run, have0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

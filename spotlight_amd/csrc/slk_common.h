@@ -241,7 +241,7 @@ struct slk_ctx {
                                       // measured default, SLK_FOLDIN_WG_MIN_LEN in slk_foldin.hip); a test / measurement switch
     int opt_user_bias_zero_hint = 1;  // 1: honour SLK_TABLES_USER_BIAS_ZERO (0: fetch the user biases regardless -- A/B and test switch)
     int64_t opt_record_nt_min_bytes = (int64_t)192 << 20;  // records of a minibatch from this size on are stored non-temporally
-                                   // (slk_bilinear.hip::do_passes; 0: never)
+                                   // (slk_bilinear.hip::run_passes; 0: never)
     slk_prep_bufs pb[2];             // double-buffered: prep(c+1) overlaps passes(c)
     hipStream_t prep_stream = nullptr;
     bool prep_warmed = false;           // the one-off tiny prep on the prep stream has run (slk_bilinear_reserve)
@@ -278,6 +278,8 @@ struct slk_ctx {
         int64_t n = 0, bsz = 0, nc0 = 0;
         int loss = 0, nn = 0;
         bool all = false;           // the negatives of the WHOLE call were drawn ahead (into pf_neg), not only the first chunk's
+        bool sgl_on = false;        // the chunk's sorts made the single-occurrence flags (prep_single_flags): a call that reads them and
+                                    //   adopts a chunk without makes them itself (slk_bilinear.hip::run_pipelined)
     } pf;
     slk_buf pf_neg;                 // uint32[n * negatives per interaction] of such a call
     slk_buf call_neg;               // the negatives of a whole (multi-chunk, not prefetched) training call: ONE draw (slk_bilinear.hip)

@@ -891,7 +891,7 @@ int slk_epoch_run_chunk(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim
                         int64_t bsz, unsigned ubits, unsigned ibits, int loss, int NP, int RS, float *snap, float *gsn,
                         float *d_mb_loss, const float *d_ratings, hipStream_t s) {
     const int mode = epoch_mode_of(loss);
-    const bool expl = mode == SLK_EMODE_EXPLICIT;  // d_ratings: the chunk's ratings, indexed by pb.uval[1] (see do_sort)
+    const bool expl = mode == SLK_EMODE_EXPLICIT;  // d_ratings: the chunk's ratings, indexed by pb.uval[1] (see prep_sort)
     const bool adp = mode == SLK_EMODE_ADAPTIVE;   // NP = 1 + negatives per interaction (pair losses 2, explicit 1)
     int vec, g, rc;
     if (!slk_pick_layout(tables->dim, &vec, &g)) return slk_fail(ctx, SLK_EINVAL, "embedding dim %d unsupported", tables->dim);

@@ -637,7 +637,7 @@ int slk_sort_pairs_any(slk_ctx *ctx, int kind, const void *kin, void *kout, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// the training prep's sorts (slk_bilinear.hip::do_sort): keys built by the first pass, one segment per minibatch
+// the training prep's sorts (slk_bilinear.hip::prep_sort): keys built by the first pass, one segment per minibatch
 // ---------------------------------------------------------------------------------------------------------------------------
 // Is a chunk of minibatches of `seg_len` pairs each sorted as segments (on the id bits only)?  Short segments are not: their
 // last tiles would be mostly empty -- the chunk is then one array sorted on (minibatch, id).

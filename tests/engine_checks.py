@@ -1545,6 +1545,53 @@ def check_user_pingpong_is_bit_neutral(be, loss, opt, D, U, I, N, B, seed=53, op
         assert not np.array_equal(results[0][1], params[0].astype(np.float32))  # (the user rows did train)
 
 
+def check_prefetch_before_pingpong_begin(be, loss, D=8, U=60, I=2000, N=700, B=128, seed=71):
+    """A first chunk prepared ahead (slk_bilinear_prefetch) BEFORE slk_user_pingpong_begin was sorted without the single-occurrence
+    flags that the training call inside the scope reads (option "item_single_min_items"): the call that adopts it makes them
+    itself.  Both orders -- prefetch, then the scope; the scope, then the prefetch -- against plain training (no scope, nothing
+    prepared ahead): every table and its first state tensor bit for bit, the chunk was adopted, the fast path did run.  Three
+    chunks of two minibatches."""
+    eng = be.engine
+    rs = np.random.RandomState(seed)
+    users, items = rs.randint(0, U, N).astype(np.int64), rs.randint(0, I, N).astype(np.int64)
+    params = [rs.normal(0, 0.1, (U, D)), rs.normal(0, 0.1, (I, D)), rs.normal(0, 0.1, U), rs.normal(0, 0.1, I)]
+    state = np.random.RandomState(seed + 1).get_state()
+    n_mb = (N + B - 1) // B
+    options = dict(chunk_interactions=256, overlap_prep=1, overlap_min_batch=0, epoch_kernel=0, item_single_min_items=1, user_lat_max_batch=0)
+    saved = {k: eng.get_option(k) for k in options}
+    results = {}
+    for k, v in options.items():
+        eng.set_option(k, v)
+    try:
+        for order in ('plain', 'prefetch_then_scope', 'scope_then_prefetch'):
+            dev = be.model(params, opt='adagrad', lr=0.05)
+            d_users, d_items = be.alloc(users), be.alloc(items)
+            mb_loss = be.alloc(np.zeros(n_mb, dtype=np.float32))
+            eng.rng_set_state(state)
+            prefetched, single = eng.get_stat('prefetched_chunks'), eng.get_stat('single_minibatches')
+
+            def prefetch():
+                eng.bilinear_prefetch(dev.tables, dev.optim, be.ptr(d_users), be.ptr(d_items), N, B, loss, 1, stream=be.stream)
+                assert eng.get_stat('prefetch_pending') > 0
+
+            if order == 'prefetch_then_scope':
+                prefetch()
+            with eng.user_pingpong(dev.tables, dev.optim, stream=be.stream, enabled=order != 'plain'):
+                if order == 'scope_then_prefetch':
+                    prefetch()
+                eng.bilinear_train(dev.tables, dev.optim, be.ptr(d_users), be.ptr(d_items), N, B, loss, 1, be.ptr(mb_loss), stream=be.stream)
+            if order != 'plain':
+                assert eng.get_stat('prefetched_chunks') == prefetched + 1, order
+                assert eng.get_stat('single_minibatches') > single, order  # (every one of the 6 minibatches at the default shape)
+            results[order] = [be.get(x).copy() for x in dev.p + dev.s1]
+    finally:
+        for k, v in saved.items():
+            eng.set_option(k, v)
+    for order in ('prefetch_then_scope', 'scope_then_prefetch'):
+        for t, (a, b) in enumerate(zip(results[order], results['plain'])):
+            assert np.array_equal(a, b), ('tensor %d of %s differs from plain training' % (t, order))
+
+
 def check_user_pingpong_contract(be):
     """include/spotlight_hip.h, slk_user_pingpong_begin: what the scope covers and refuses, and its lifetime rules -- one scope per
     ctx, plain tables + row-sparse optimizers; calls that would read the caller's (mixed) user table are refused inside it; so

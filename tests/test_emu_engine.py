@@ -76,6 +76,11 @@ def test_single_occurrence_fast_path_is_bit_neutral(be, loss):
     assert be.engine.get_stat('single_minibatches') == n1  # (Adagrad only)
 
 
+@pytest.mark.parametrize('loss', ['bpr', 'pointwise', 'hinge'])
+def test_prefetch_before_pingpong_begin(be, loss):
+    ec.check_prefetch_before_pingpong_begin(be, loss)
+
+
 def test_user_pingpong_contract(be):
     ec.check_user_pingpong_contract(be)
 
