@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from spotlight_amd import _epochs  # noqa: E402
 from spotlight_amd.factorization import implicit as host  # noqa: E402
 from spotlight_amd.factorization.implicit import ImplicitFactorizationModel  # noqa: E402
 from spotlight_amd.interactions import Interactions  # noqa: E402
@@ -38,7 +39,7 @@ def main():
     torch.cuda.synchronize()
     eng = host._engine_for(torch.device('cuda', torch.cuda.current_device()))
     base_fit = dict(host._FIT_OPTIONS)
-    real_shuffle = host.device_epoch_shuffle
+    real_shuffle = _epochs.device_epoch_shuffle  # (every fit() schedule resolves the call in spotlight_amd/_epochs.py)
     out_f = open(args.out, 'a') if args.out else None
     configs = list(args.configs)
     configs = configs + configs[:1]
@@ -68,9 +69,9 @@ def main():
                     real_shuffle(engine, random_state, n_, d_perm, arrays, stream)
                 finally:
                     engine.shuffle_perm = real_perm
-            host.device_epoch_shuffle = identity_shuffle
+            _epochs.device_epoch_shuffle = identity_shuffle
         else:
-            host.device_epoch_shuffle = real_shuffle
+            _epochs.device_epoch_shuffle = real_shuffle
         with eng.options(**ctx_opts):
             times, steady = [], []
             for _ in range(args.repeat):
@@ -95,7 +96,7 @@ def main():
             out_f.flush()
     host._FIT_OPTIONS.clear()
     host._FIT_OPTIONS.update(base_fit)
-    host.device_epoch_shuffle = real_shuffle
+    _epochs.device_epoch_shuffle = real_shuffle
 
 
 if __name__ == '__main__':

@@ -196,6 +196,57 @@ class SlkError(RuntimeError):
         self.code = code
 
 
+class _OptionScope(object):
+    """Engine.options(): the given ctx options for the duration of the block, the previous values on every way out."""
+
+    def __init__(self, engine, values):
+        self.engine, self.values, self.saved = engine, values, []
+
+    def __enter__(self):
+        self.saved = [(k, self.engine.get_option(k)) for k in self.values]
+        for k, v in self.values.items():
+            self.engine.set_option(k, v)
+        return self.engine
+
+    def __exit__(self, *exc):
+        for k, v in reversed(self.saved):
+            self.engine.set_option(k, v)
+        return False
+
+
+class _TableScope(object):
+    """Engine.bias_shadow() / Engine.user_pingpong(): the `begin` entry point on the way in, `end` (the write-back into the
+    caller's tensors) on every way out, both on `stream`.  `active`: the ctx really holds the scope -- it does not if
+    `enabled` is false or the copy did not fit (the scope is an optimisation, never a requirement: 8 bytes per item row are
+    0.8 GB at 10^8 rows, a second user table more; training goes on in the plain layout, bit-identically).
+    __exit__ is idempotent."""
+
+    def __init__(self, engine, begin, end, abort, tables, optim, stream, enabled):
+        self.engine, self._begin, self._end, self._abort = engine, begin, end, abort
+        self.tables, self.optim, self.stream, self.enabled = tables, optim, stream, enabled
+        self.active = False
+
+    def __enter__(self):
+        if self.enabled:
+            rc = self._begin(self.engine._ctx, C.byref(self.tables), C.byref(self.optim), C.c_void_p(self.stream))
+            if rc != SLK_ENOMEM:
+                self.engine._check(rc)
+                self.active = True
+        return self.engine
+
+    def __exit__(self, *exc):
+        if self.active:
+            self.active = False
+            self.engine._check(self._end(self.engine._ctx, C.c_void_p(self.stream)))
+        return False
+
+    def abort(self):
+        """Close the scope without writing back (the caller's arrays are gone): the `abort` entry point."""
+        if self.active:
+            self.active = False
+            self.engine._check(self._abort(self.engine._ctx))
+
+
 class Engine(object):
     """One slk_ctx.  All pointer arguments are raw integer addresses of device memory
     (torch `tensor.data_ptr()`), `stream` is a raw hipStream_t (0 = default stream)."""
@@ -246,85 +297,22 @@ class Engine(object):
             with engine.options(overlap_prep=1):
                 ... training calls ...
         """
-        engine = self
-
-        class _Scoped(object):
-            def __enter__(self_):
-                self_.saved = [(k, engine.get_option(k)) for k in values]
-                for k, v in values.items():
-                    engine.set_option(k, v)
-                return engine
-
-            def __exit__(self_, *exc):
-                for k, v in reversed(self_.saved):
-                    engine.set_option(k, v)
-                return False
-        return _Scoped()
+        return _OptionScope(self, values)
 
     def bias_shadow(self, tables, optim, stream=0, enabled=True):
         """include/spotlight_hip.h: slk_bias_shadow_begin / _end as a context manager -- the item biases and their Adagrad
         accumulator interleaved for the duration of the block (the caller's tensors are stale inside it and rewritten on every
         way out).  `enabled=False`: a no-op scope."""
-        engine = self
-
-        class _Shadow(object):
-            active = False
-
-            def __enter__(self_):
-                if enabled:
-                    rc = engine._lib.slk_bias_shadow_begin(engine._ctx, C.byref(tables), C.byref(optim), C.c_void_p(stream))
-                    if rc == SLK_ENOMEM:
-                        # 8 bytes per item row did not fit (0.8 GB at 10^8 rows): the scope is an optimisation, never a
-                        # requirement -- training goes on in the two-array layout, bit-identically (ADVICE r05)
-                        return engine
-                    engine._check(rc)
-                    self_.active = True
-                return engine
-
-            def __exit__(self_, *exc):
-                if self_.active:
-                    self_.active = False
-                    engine._check(engine._lib.slk_bias_shadow_end(engine._ctx, C.c_void_p(stream)))
-                return False
-
-            def abort(self_):
-                """Close the scope without writing back (the caller's arrays are gone): slk_bias_shadow_abort."""
-                if self_.active:
-                    self_.active = False
-                    engine._check(engine._lib.slk_bias_shadow_abort(engine._ctx))
-        return _Shadow()
+        lib = self._lib
+        return _TableScope(self, lib.slk_bias_shadow_begin, lib.slk_bias_shadow_end, lib.slk_bias_shadow_abort, tables, optim, stream, enabled)
 
     def user_pingpong(self, tables, optim, stream=0, enabled=True):
         """include/spotlight_hip.h: slk_user_pingpong_begin / _end as a context manager -- the user embedding table doubled for
         the duration of the block: the user pass writes updated rows to the other copy, the item pass gathers pre-step rows
         where they still stand, no record is written (the caller's tensor is a mix of rows inside the block and made whole on
         every way out).  `enabled=False`: a no-op scope."""
-        engine = self
-
-        class _PingPong(object):
-            active = False
-
-            def __enter__(self_):
-                if enabled:
-                    rc = engine._lib.slk_user_pingpong_begin(engine._ctx, C.byref(tables), C.byref(optim), C.c_void_p(stream))
-                    if rc == SLK_ENOMEM:  # the second copy did not fit: the scope is an optimisation, never a requirement
-                        return engine
-                    engine._check(rc)
-                    self_.active = True
-                return engine
-
-            def __exit__(self_, *exc):
-                if self_.active:
-                    self_.active = False
-                    engine._check(engine._lib.slk_user_pingpong_end(engine._ctx, C.c_void_p(stream)))
-                return False
-
-            def abort(self_):
-                """Close the scope without writing back (the caller's arrays are gone): slk_user_pingpong_abort."""
-                if self_.active:
-                    self_.active = False
-                    engine._check(engine._lib.slk_user_pingpong_abort(engine._ctx))
-        return _PingPong()
+        lib = self._lib
+        return _TableScope(self, lib.slk_user_pingpong_begin, lib.slk_user_pingpong_end, lib.slk_user_pingpong_abort, tables, optim, stream, enabled)
 
     def get_stat(self, name):
         """include/spotlight_hip.h: slk_ctx_get_stat (diagnostics of the last calls)."""

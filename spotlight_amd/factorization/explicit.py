@@ -7,13 +7,47 @@ negatives and the regression / poisson / logistic losses of spotlight/losses.py:
 error behaviour and random-state consumption as the reference (one draw in the constructor, one
 numpy-exact shuffle of the three arrays per epoch, computed on the device).
 """
+import contextlib
+
 import numpy as np
 import torch
 
+from spotlight_amd import _epochs
 from spotlight_amd.factorization._components import _predict_process_ids
 from spotlight_amd.factorization import implicit as _host
 from spotlight_amd.factorization.implicit import ImplicitFactorizationModel
 from spotlight_amd.torch_utils import set_seed
+
+
+class _ExplicitEpochs(object):
+    """What the schedules of spotlight_amd/_epochs.py ask of the explicit-feedback model: the shuffle of the three arrays and
+    slk_bilinear_train_explicit.  `lane_stream`: the raw stream of the two-lane schedule's prep lane (two sets of epoch
+    buffers, the ratings converted on that stream); None under the serial schedule (one set, this thread's stream)."""
+
+    def __init__(self, model, binding, tables, sources, device, lane_stream=None):
+        self.binding, self.tables, self.sources, self.n = binding, tables, sources, sources[0].numel()
+        self.call = (self.n, model._batch_size, model._loss)
+        self.mb_loss = torch.empty((self.n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
+        self.slots = [[torch.empty_like(d) for d in sources] + [torch.empty(self.n, dtype=torch.float32, device=device)]
+                      for _ in range(1 if lane_stream is None else 2)]
+        self.d_perm = torch.empty(self.n, dtype=torch.int64, device=device)
+        self.side = (torch.cuda.ExternalStream(lane_stream, device=device)
+                     if lane_stream is not None and device.type == 'cuda' else None)
+
+    def prepare(self, engine, stream, random_state, epoch_num):
+        slot = self.slots[epoch_num % len(self.slots)]
+        _epochs.device_epoch_shuffle(engine, random_state, self.n, self.d_perm,
+                                     [(src, dst, 1) for src, dst in zip(self.sources, slot)], stream)
+        # (on the prep lane's stream where there is one: the state read-back that follows then covers the conversion too)
+        with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+            slot[3].view(torch.int32).copy_(slot[2])  # the float32 bit patterns back out of their int64 carriers
+
+    def train(self, engine, stream, epoch_num):
+        d_users, d_items, _, d_ratings = self.slots[epoch_num % len(self.slots)]
+        ostruct = self.binding.as_struct()
+        engine.bilinear_train_explicit(self.tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), d_ratings.data_ptr(),
+                                       *self.call, self.mb_loss.data_ptr(), stream=stream)
+        self.binding.store_steps(ostruct.step)
 
 
 class ExplicitFactorizationModel(ImplicitFactorizationModel):
@@ -70,88 +104,21 @@ class ExplicitFactorizationModel(ImplicitFactorizationModel):
         device = self._net.tables()[0].device
         engine = _host._engine_for(device)
         stream = _host._stream_for(device)
-        tables = self._slk_tables()
         n = len(user_ids)
-        n_minibatches = (n + self._batch_size - 1) // self._batch_size
-        mb_loss = torch.empty(n_minibatches, dtype=torch.float32, device=device)
-
         # ids and ratings go to the device once; the ratings ride through the shuffle as int64 bit
         # patterns (slk_gather_rows_i64 moves 8-byte elements)
         ratings = np.ascontiguousarray(interactions.ratings, dtype=np.float32)
-        d_users0 = _host.ids_to_device(user_ids, device)
-        d_items0 = _host.ids_to_device(item_ids, device)
-        d_ratings0 = torch.from_numpy(ratings).to(device).view(torch.int32).to(torch.int64)
+        sources = [_host.ids_to_device(user_ids, device), _host.ids_to_device(item_ids, device),
+                   torch.from_numpy(ratings).to(device).view(torch.int32).to(torch.int64)]
+        # The reference's README example fits MovieLens-100K with batch_size 256: training draws nothing from the RandomState,
+        # so epochs of that scale shuffle epoch e + 1 on a second slk_ctx / HIP stream while epoch e trains (_epochs.run_two_lane).
+        # Same permutations, same RandomState afterwards, bit-identical tables.
         if self._n_iter > 1 and n <= _host._PIPELINE_MAX_DRAWS:
-            return self._fit_pipelined(binding, engine, device, stream, tables, d_users0, d_items0, d_ratings0, n, mb_loss,
-                                       verbose)
-        d_users, d_items, d_rbits = (torch.empty_like(d_users0), torch.empty_like(d_items0),
-                                     torch.empty_like(d_ratings0))
-        d_perm = torch.empty(n, dtype=torch.int64, device=device)
-        for epoch_num in range(self._n_iter):
-            engine.rng_set_state(self._random_state.get_state())
-            _host.device_epoch_shuffle(engine, self._random_state, n, d_perm,
-                                       [(d_users0, d_users, 1), (d_items0, d_items, 1), (d_ratings0, d_rbits, 1)],
-                                       stream)
-            d_ratings = d_rbits.to(torch.int32).view(torch.float32)
-            ostruct = binding.as_struct()
-            engine.bilinear_train_explicit(tables, ostruct, d_users.data_ptr(), d_items.data_ptr(),
-                                           d_ratings.data_ptr(), n, self._batch_size, self._loss, mb_loss.data_ptr(),
-                                           stream=stream)
-            binding.store_steps(ostruct.step)
-            self._random_state.set_state(engine.rng_get_state())  # synchronises the stream
-
-            epoch_loss = float(mb_loss.double().mean().item())
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
-
-    def _fit_pipelined(self, binding, engine, device, stream, tables, d_users0, d_items0, d_ratings0, n, mb_loss, verbose):
-        """The epoch loop for datasets of the reference's own scale (its README example fits MovieLens-100K with batch_size
-        256): training draws nothing from the RandomState, so epoch e + 1's shuffle is computed on a second slk_ctx / HIP
-        stream while epoch e trains (see ImplicitFactorizationModel._fit_pipelined).  Same permutations, same RandomState
-        afterwards, bit-identical tables."""
-        prep, prep_stream = _host._prep_lane_for(device)
-        torch.cuda.current_stream(device).synchronize() if device.type == 'cuda' else None  # the uploads are complete
-        bufs = [(torch.empty_like(d_users0), torch.empty_like(d_items0), torch.empty_like(d_ratings0),
-                 torch.empty(n, dtype=torch.float32, device=device)) for _ in range(2)]
-        d_perm = torch.empty(n, dtype=torch.int64, device=device)
-        side = torch.cuda.ExternalStream(prep_stream, device=device) if device.type == 'cuda' else None
-
-        def prepare(slot):
-            prep.rng_set_state(self._random_state.get_state())
-            d_users, d_items, d_rbits, d_ratings = bufs[slot]
-            _host.device_epoch_shuffle(prep, self._random_state, n, d_perm,
-                                       [(d_users0, d_users, 1), (d_items0, d_items, 1), (d_ratings0, d_rbits, 1)], prep_stream)
-            if side is not None:
-                with torch.cuda.stream(side):
-                    d_ratings.copy_(d_rbits.to(torch.int32).view(torch.float32))
-            else:
-                d_ratings.copy_(d_rbits.to(torch.int32).view(torch.float32))
-            self._random_state.set_state(prep.rng_get_state())  # synchronises the prep stream (the conversion included)
-
-        prepare(0)
-        for epoch_num in range(self._n_iter):
-            d_users, d_items, _, d_ratings = bufs[epoch_num % 2]
-            ostruct = binding.as_struct()
-            engine.bilinear_train_explicit(tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), d_ratings.data_ptr(), n,
-                                           self._batch_size, self._loss, mb_loss.data_ptr(), stream=stream)
-            binding.store_steps(ostruct.step)
-            state_after_epoch = self._random_state.get_state()
-            if epoch_num + 1 < self._n_iter:
-                prepare((epoch_num + 1) % 2)  # overlaps the training kernels of this epoch
-
-            epoch_loss = float(mb_loss.double().mean().item())  # also waits for this epoch's kernels
-            engine.check()
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                self._random_state.set_state(state_after_epoch)
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+            lane = _host._prep_lane_for(device)
+            job = _ExplicitEpochs(self, binding, self._slk_tables(), sources, device, lane_stream=lane[1])
+            return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
+        job = _ExplicitEpochs(self, binding, self._slk_tables(), sources, device)
+        return _epochs.run_serial(engine, stream, self._random_state, self._n_iter, verbose, job)
 
     def fold_in(self, interactions, n_iter=None, init=None, negatives=None):
         raise NotImplementedError('fold_in() of the explicit-feedback model is not built (INTEGRATION.md 2m): its step needs the new '

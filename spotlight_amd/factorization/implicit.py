@@ -4,13 +4,12 @@ Same constructor, fit(), predict(), error messages and random-state behaviour as
 reference; everything inside the epoch loop (negative sampling, both forward passes, loss,
 backward, optimizer update) is one C-ABI call into csrc/libspotlight_hip.so per epoch.
 """
-import time
-
 import numpy as np
 import torch
 import torch.optim as optim
 
-from spotlight_amd import _native
+from spotlight_amd import _epochs, _native
+from spotlight_amd._epochs import IdUpload, device_epoch_shuffle, ids_to_device  # noqa: F401 -- reached through this module
 from spotlight_amd.factorization._components import _predict_process_ids
 from spotlight_amd.factorization.representations import BilinearNet
 from spotlight_amd.helpers import _repr_model
@@ -20,7 +19,7 @@ from spotlight_amd.torch_utils import set_seed
 _ENGINES = {}
 # fit(): epochs of at most this many negative draws prepare the next epoch while training.  Larger epochs do not gain:
 # at 10^8 interactions the two lanes time-slice the chip (train 71 ms + prepare 38 ms alone, 100 ms together:
-# profiles/r02_m_fit_pipelined_at_1e8_no_gain.json)
+# profiles/r02_m_*_at_1e8_no_gain.json)
 _PIPELINE_MAX_DRAWS = 1 << 22
 _DEFERRED_CHECK_MIN = 1 << 22  # ids per fit() from which the id-range checks run on worker threads beside the upload
 _PREFETCH = True  # large epochs: the next epoch's first chunk is prepared beside the last passes of this one (test switch)
@@ -96,140 +95,6 @@ def _state_tensor(state, key, like):
     if key not in state:
         state[key] = torch.zeros_like(like, memory_format=torch.preserve_format)
     return state[key]
-
-
-def ids_to_device(ids, device):
-    """int64 device tensor of a host id array: uploaded in the array's own dtype (int32 in the reference's
-    datasets: half the PCIe bytes) and widened on the device, instead of widening on the host first."""
-    ids = np.ascontiguousarray(ids)
-    if ids.dtype not in (np.int32, np.int64):
-        ids = ids.astype(np.int64)
-    return torch.from_numpy(ids).to(device).to(torch.int64)
-
-
-def device_epoch_shuffle(engine, random_state, n, d_perm, arrays, stream):
-    """d_dst = d_src[numpy-exact shuffle of arange(n)] for every (d_src, d_dst, row_len) of `arrays`,
-    drawn from the engine's RNG state (slk_shuffle_perm: the reference's `shuffle`, torch_utils.py:35-52).
-    If the device shuffle reports a failure (it cannot, short of a 12-sigma rejection tail) the
-    permutation is drawn by numpy on the host from `random_state`, as the reference does, and the
-    engine's RNG state is re-synchronised -- the results are identical either way.
-    `arrays` may be a callable returning the list: it is called AFTER the permutation has been drawn (the permutation
-    needs only n, so an upload of the ids can still be in flight while it is computed: IdUpload)."""
-    try:
-        engine.shuffle_perm(n, d_perm.data_ptr(), stream=stream)
-    except _native.SlkError:
-        order = np.arange(n)
-        random_state.shuffle(order)
-        d_perm.copy_(torch.from_numpy(order))
-        engine.rng_set_state(random_state.get_state())
-    if callable(arrays):
-        arrays = arrays()
-    for entry in arrays:
-        if len(entry) == 4:  # ('pairs', d_pairs, d_users_dst, d_items_dst): both id arrays from their packed form in one pass
-            _, d_pairs, d_users_dst, d_items_dst = entry
-            engine.gather_id_pairs(d_pairs.data_ptr(), d_perm.data_ptr(), n, d_users_dst.data_ptr(), d_items_dst.data_ptr(),
-                                   stream=stream)
-            continue
-        d_src, d_dst, row_len = entry
-        engine.gather_rows_i64(d_src.data_ptr(), d_perm.data_ptr(), n, row_len, d_dst.data_ptr(), stream=stream)
-
-
-class IdUpload(object):
-    """The host -> HBM copy of fit()'s id arrays on a worker thread (ids_to_device; the copies release the GIL), so that the
-    first epoch's permutation -- which needs only len(ids) -- is drawn on the GPU meanwhile.  result() joins and returns the
-    int64 device tensors; the copies run on the worker's (default) stream, and a pageable copy has completed when the call
-    returns, so after the join the data is in place for any stream."""
-
-    def __init__(self, arrays, device):
-        import threading
-        self._out = [None] * len(arrays)
-        self._err = []
-
-        def work():
-            try:
-                if device.type == 'cuda':
-                    torch.cuda.set_device(device)
-                for k, a in enumerate(arrays):
-                    self._out[k] = ids_to_device(a, device)
-                if device.type == 'cuda':
-                    torch.cuda.current_stream(device).synchronize()  # the widening kernels on this thread's stream
-            except BaseException as e:  # re-raised by result()
-                self._err.append(e)
-        self._thread = threading.Thread(target=work, name='spotlight-id-upload')
-        self._thread.start()
-
-    def result(self):
-        self._thread.join()
-        if self._err:
-            raise self._err[0]
-        return self._out
-
-
-class _Background(object):
-    """fn() on a worker thread (or at once); join() returns its value or re-raises what it raised.  (Module level on purpose: a
-    class created inside fit() would form a reference cycle through its closure and keep the epoch's id buffers -- GBs at
-    bench scale -- out of the caching allocator until the cyclic collector runs; the next fit() then paid 20-50 ms of
-    hipMalloc, profiles/r04_t_fit_first_epoch_probe.txt.)"""
-
-    def __init__(self, fn, threaded):
-        self._fn, self._out, self._err, self._thread = fn, None, None, None
-        if threaded:
-            import threading
-            self._thread = threading.Thread(target=self._run, name='spotlight-epoch-shuffle')
-            self._thread.start()
-        else:
-            self._run()
-
-    def _run(self):
-        try:
-            self._out = self._fn()
-        except BaseException as e:  # noqa: BLE001 -- re-raised by join()
-            self._err = e
-        self._fn = None
-
-    def join(self):
-        if self._thread is not None:
-            self._thread.join()
-            self._thread = None
-        if self._err is not None:
-            raise self._err
-        return self._out
-
-
-class _Deferred(object):
-    """Every function of `fns` now, or each on a worker thread of its own; result() joins and re-raises the first error in
-    the order of `fns` (the order the serial checks would have raised in)."""
-
-    def __init__(self, fns, threaded):
-        self.threaded = bool(threaded)
-        self._errs, self._threads = [None] * len(fns), []
-
-        def work(k):
-            try:
-                fns[k]()
-            except BaseException as e:  # noqa: BLE001 -- re-raised by result()
-                self._errs[k] = e
-        for k in range(len(fns)):
-            if self.threaded:
-                import threading
-                self._threads.append(threading.Thread(target=work, args=(k,), name='spotlight-id-check'))
-                self._threads[-1].start()
-            else:
-                work(k)
-                if self._errs[k] is not None:
-                    break
-
-    def join(self):
-        for t in self._threads:
-            t.join()
-        self._threads = []
-
-    def result(self):
-        self.join()
-        for k, e in enumerate(self._errs):
-            if e is not None:
-                self._errs = [None] * len(self._errs)
-                raise e
 
 
 def _reject_negative_ids(ids):
@@ -326,6 +191,57 @@ class _OptimizerBinding(object):
                 s['step'].fill_(float(step))
             else:
                 s['step'] = int(step)
+
+
+class _ImplicitEpochs(object):
+    """What the schedules of spotlight_amd/_epochs.py ask of the implicit model: the epoch buffers (`slots`: (users, items) of
+    the three-stage schedule's ShuffledIds, or (users, items, negatives) of its own under the two-lane one) and the entry
+    points slk_bilinear_reserve / _prefetch / _train over the model's tables, optimizer and hyper-parameters."""
+
+    def __init__(self, model, binding, tables, n, device):
+        self.binding, self.tables, self.n, self.device, self.num_items = binding, tables, n, device, model._num_items
+        self.call = (n, model._batch_size, model._loss, model._num_negative_samples)
+        self.mb_loss = torch.empty((n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
+        self.slots, self.scopes, self.sources = [], [], None
+
+    def reserve(self, engine, stream):
+        engine.bilinear_reserve(self.tables, self.binding.as_struct(), *self.call, stream=stream)
+
+    def own_slots(self, sources, nn):
+        """Two-lane schedule: two sets of epoch buffers, shuffled from the uploaded `sources`."""
+        self.sources = sources
+        self.slots = [(torch.empty_like(sources[0]), torch.empty_like(sources[1]),
+                       torch.empty(self.n * nn, dtype=torch.int64, device=self.device)) for _ in range(2)]
+        # (the permutation AFTER the epoch buffers, all of one size class in the caching allocator: allocated first it cost a
+        # MovieLens-100K fit() 0.9 %, profiles/fit_driver_parent_vs_head.json, sessions 1 and 2)
+        self.d_perm = torch.empty(self.n, dtype=torch.int64, device=self.device)
+
+    def prepare(self, engine, stream, random_state, epoch_num):
+        d_users, d_items, d_neg = self.slots[epoch_num % 2]
+        _epochs.device_epoch_shuffle(engine, random_state, self.n, self.d_perm,
+                                     [(self.sources[0], d_users, 1), (self.sources[1], d_items, 1)], stream)
+        # one randint per minibatch == one contiguous draw over the epoch (sampling.py:34)
+        engine.sample_items(self.num_items, d_neg.numel(), d_neg.data_ptr(), stream=stream)
+
+    def open_scopes(self, stack, engine, stream):
+        shadow, pingpong = self.scopes
+        stack.enter_context(shadow)  # (from here to the scope's end the item-bias tensors are stale: nothing inside reads them)
+        stack.enter_context(pingpong)  # (... and the user-embedding tensor holds only some of the current rows)
+        if pingpong.active:  # the scope's {dL/dscore, src} pairs are wider than the one-table layout's side array: grown now,
+            self.reserve(engine, stream)  # not inside the first training call
+
+    def prefetch(self, engine, stream, epoch_num, state):
+        d_users, d_items = self.slots[epoch_num % len(self.slots)]
+        engine.bilinear_prefetch(self.tables, self.binding.as_struct(), d_users.data_ptr(), d_items.data_ptr(), *self.call,
+                                 state=state, stream=stream)
+
+    def train(self, engine, stream, epoch_num):
+        slot = self.slots[epoch_num % len(self.slots)]
+        d_neg = slot[2].data_ptr() if len(slot) > 2 else None  # (handed in under the two-lane schedule, else drawn by the call)
+        ostruct = self.binding.as_struct()
+        engine.bilinear_train(self.tables, ostruct, slot[0].data_ptr(), slot[1].data_ptr(), *self.call, self.mb_loss.data_ptr(),
+                              d_neg_in=d_neg, stream=stream)
+        self.binding.store_steps(ostruct.step)
 
 
 class ImplicitFactorizationModel(object):
@@ -475,14 +391,10 @@ class ImplicitFactorizationModel(object):
         # path they run on worker threads beside the id upload and the first epoch's shuffle; their verdict is collected before
         # the first training call is enqueued (nothing the caller can observe has changed by then: the RandomState is restored,
         # the tables are untouched).
-        check = _Deferred(self._id_checks(user_ids, item_ids),
-                          threaded=not (autograd or small) and n >= _DEFERRED_CHECK_MIN)
+        check = _epochs._Deferred(self._id_checks(user_ids, item_ids),
+                                  threaded=not (autograd or small) and n >= _DEFERRED_CHECK_MIN)
         if not check.threaded:
             check.result()
-        # diagnostic: set model._fit_timeline = [] before fit() to collect (label, host time) marks of the large-epoch loop
-        tl = getattr(self, '_fit_timeline', None)
-        mark = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None else (lambda label: None)
-        mark('checks started')
         if autograd:
             return self._fit_autograd(user_ids, item_ids, verbose)
         binding = self._bind()
@@ -496,225 +408,27 @@ class ImplicitFactorizationModel(object):
         if (self._loss in ('bpr', 'hinge') and binding.kind in ('adagrad', 'sgd') and not tables.user_bloom and not tables.item_bloom
                 and not bool(self._net.tables()[2].any())):
             tables.flags |= _native.TABLES_USER_BIAS_ZERO
-        n_minibatches = (n + self._batch_size - 1) // self._batch_size
-        mb_loss = torch.empty(n_minibatches, dtype=torch.float32, device=device)
-
-        engine.bilinear_reserve(tables, binding.as_struct(), n, self._batch_size, self._loss,
-                                self._num_negative_samples, stream=stream)
-        mark('scratch reserved')
+        job = _ImplicitEpochs(self, binding, tables, n, device)
+        job.reserve(engine, stream)
+        lane = _prep_lane_for(device)
         # ids go to the device once (on a worker thread: the first epoch's permutation is drawn meanwhile); every epoch's
         # permutation x[shuffle_indices] of them (torch_utils.py:35-52) is computed there, bit-exact with numpy's Fisher-Yates
         if small:
-            d_users0, d_items0 = IdUpload([user_ids, item_ids], device).result()
-            return self._fit_pipelined(binding, engine, device, stream, tables, d_users0, d_items0, n, nn, mb_loss, verbose)
-        # Large epochs: a three-stage pipeline over epochs (round 4), every stage consuming the ONE MT19937 stream in the
-        # reference's order -- shuffle(e), negatives(e), shuffle(e + 1), ... (implicit.py:212-221, torch_utils.py:46-47,
-        # sampling.py:34):
-        #   train lane   the passes of epoch e (slk_bilinear_train; it draws nothing: its negatives exist already)
-        #   prep stream  the negatives of the WHOLE epoch e + 1 and the sorts of its first chunk (slk_bilinear_prefetch), drawn
-        #                beside the last passes of epoch e as soon as epoch e's training call has been enqueued
-        #   prep lane    the shuffle + id gathers of epoch e + 2 on the second slk_ctx / HIP stream, from the stream position
-        #                behind epoch e + 1's negatives -- known an epoch ahead (slk_rng_get_state_sampled); on a worker thread,
-        #                because the numpy-exact shuffle reads counts back and would hold the host up
-        # so that in the steady state nothing but the passes is on the critical path.  Same ids, negatives and RandomState as
-        # the serial loop, bit-identical tables (tests/test_host_model.py, tests/test_gpu_model.py).  Before: 28.9 ms per epoch
-        # at 2^25 interactions, of which 3.3 ms shuffle and 2.1 ms first-chunk prep ran with no pass beside them
-        # (profiles/r04_m_fit_epoch_breakdown.txt).
-        prep, prep_stream = _prep_lane_for(device)
-        threaded = _PREFETCH and prep is not engine and engine._lib is _native._LIB  # (the test harness's emulator is single-threaded)
-        n_slots = min(self._n_iter, 3 if _PREFETCH else 2)
-        bufs = [(torch.empty(n, dtype=torch.int64, device=device), torch.empty(n, dtype=torch.int64, device=device))
-                for _ in range(max(n_slots, 1))]
-        d_perm = torch.empty(n, dtype=torch.int64, device=device)
-        d_pairs = unpacked = None
-        # (the upload starts AFTER the epoch buffers exist: its worker allocates from the same caching allocator, and racing it
-        # for the blocks the previous fit() left there sent this thread to hipMalloc, 15 ms per pair of buffers)
-        mark('epoch buffers')
-        upload = IdUpload([user_ids, item_ids], device)
-
-        def shuffle_into(slot, state):
-            """bufs[slot] = ids[numpy-exact shuffle] drawn from `state` on the prep lane; returns the state behind the shuffle
-            (reading it waits for the prep lane's stream: the gathers are complete)."""
-            def sources():
-                # the uploaded ids, packed once per fit() into (user, item) pairs of 32 bits: a shuffled interaction is then
-                # ONE random 8-byte read for both arrays (slk_gather_id_pairs)
-                nonlocal d_pairs, unpacked
-                if d_pairs is None:
-                    unpacked = upload.result()  # (kept until the prep lane has been waited for, below)
-                    upload._out = None
-                    d_pairs = torch.empty(2 * n, dtype=torch.int32, device=device)
-                    # INVARIANT (ADVICE r04): with the id checks on worker threads (`check.threaded`) these ids are NOT validated
-                    # yet -- they are truncated to uint32, permuted and gathered as DATA only.  Nothing may index a table with
-                    # them, and no training call or prefetch may be enqueued, before `check.result()` has returned
-                    # (tests/test_host_model.py::test_id_checks_on_worker_threads_raise_like_the_serial_ones).
-                    prep.pack_id_pairs(unpacked[0].data_ptr(), unpacked[1].data_ptr(), n, d_pairs.data_ptr(), stream=prep_stream)
-                return [('pairs', d_pairs, bufs[slot][0], bufs[slot][1])]
-            fallback = np.random.RandomState()  # (device_epoch_shuffle's host fall-back draws from it: private to this job)
-            fallback.set_state(state)
-            if device.type == 'cuda':
-                torch.cuda.set_device(device)
-            prep.rng_set_state(state)
-            nonlocal unpacked
-            device_epoch_shuffle(prep, fallback, n, d_perm, sources, prep_stream)
-            after = prep.rng_get_state()
-            unpacked = None  # the 64-bit copies of the ids: packed by now
-            return after
-
-        def _Job(slot, state):
-            # shuffle_into on a worker thread (or at once, under the single-threaded test harness)
-            return _Background(lambda: shuffle_into(slot, state), threaded)
-
-        if self._n_iter <= 0:  # nothing to train: no shuffle is drawn, the RandomState stays where it is (as in the reference)
-            upload.result()
-            check.result()
-            return
-        mark('loop set up')
-        # self._random_state runs AHEAD of training; `consumed` is the state the reference would hold at this point -- restored on
-        # every way out, the normal one included
-        consumed = self._random_state.get_state()
-        job = None
-        shadow = engine.bias_shadow(tables, binding.as_struct(), stream=stream,
-                                    enabled=(binding.kind == 'adagrad' and self._num_items >= _BIAS_SHADOW_MIN_ITEMS and
-                                             self._batch_size >= 4096 and not tables.item_bloom))
-        shadowed = False
-        pingpong = engine.user_pingpong(tables, binding.as_struct(), stream=stream,
-                                        enabled=(self._loss in ('pointwise', 'bpr', 'hinge') and binding.kind in ('adagrad', 'sparse_adam', 'sgd')
-                                                 and min(self._batch_size, n) >= _USER_PINGPONG_MIN_BATCH
-                                                 and not tables.user_bloom and not tables.item_bloom))
-        pingponged = False
-        try:
-            state = shuffle_into(0, consumed)  # the first epoch's shuffle: the one nothing hides
-            mark('shuffle 0')
-            check.result()  # raises what _check_input raised
-            shadow.__enter__()  # (from here to the `finally` the item-bias tensors are stale: nothing below reads them)
-            shadowed = True
-            pingpong.__enter__()  # (... and the user-embedding tensor holds only some of the current rows)
-            pingponged = True
-            if pingpong.active:  # the scope's {dL/dscore, src} pairs are wider than the one-table layout's side array: grown now,
-                # not inside the first training call
-                engine.bilinear_reserve(tables, binding.as_struct(), n, self._batch_size, self._loss, self._num_negative_samples,
-                                        stream=stream)
-            if _PREFETCH:
-                engine.bilinear_prefetch(tables, binding.as_struct(), bufs[0][0].data_ptr(), bufs[0][1].data_ptr(), n, self._batch_size,
-                                         self._loss, self._num_negative_samples, state=state, stream=stream)
-                after_negs = engine.rng_get_state_sampled()  # behind negatives(0) -- or `state` itself if nothing was drawn ahead
-                drawn_ahead = engine.get_stat('prefetch_pending') == 2
-            else:
-                engine.rng_set_state(state)
-                after_negs, drawn_ahead = None, False
-            if drawn_ahead and self._n_iter > 1:
-                job = _Job(1 % n_slots, after_negs)  # shuffle(1) beside the passes of epoch 0
-            mark('prefetch 0')
-            for epoch_num in range(self._n_iter):
-                d_users, d_items = bufs[epoch_num % n_slots]
-                ostruct = binding.as_struct()
-                engine.bilinear_train(tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), n,
-                                      self._batch_size, self._loss, self._num_negative_samples,
-                                      mb_loss.data_ptr(), stream=stream)
-                binding.store_steps(ostruct.step)
-                mark('train %d enqueued' % epoch_num)
-                # the state the reference holds at the end of this epoch: behind its negatives
-                consumed = after_negs if drawn_ahead else engine.rng_get_state_sampled()
-                if epoch_num + 1 < self._n_iter:
-                    nxt = (epoch_num + 1) % n_slots
-                    # shuffle(e + 1): prepared an epoch ago on the worker -- or now, beside the last passes of this epoch
-                    state = job.join() if job is not None else shuffle_into(nxt, consumed)
-                    job = None
-                    mark('shuffle %d joined' % (epoch_num + 1))
-                    if _PREFETCH:
-                        engine.bilinear_prefetch(tables, binding.as_struct(), bufs[nxt][0].data_ptr(), bufs[nxt][1].data_ptr(), n,
-                                                 self._batch_size, self._loss, self._num_negative_samples, state=state, stream=stream)
-                        after_negs = engine.rng_get_state_sampled()
-                        drawn_ahead = engine.get_stat('prefetch_pending') == 2
-                        if drawn_ahead and epoch_num + 2 < self._n_iter:
-                            job = _Job((epoch_num + 2) % n_slots, after_negs)
-                        mark('prefetch %d' % (epoch_num + 1))
-                    else:
-                        engine.rng_set_state(state)
-
-                # mean of per-minibatch loss.item() (implicit.py:240,245): one D2H per epoch; also waits for the epoch's kernels
-                epoch_loss = float(mb_loss.double().mean().item())
-                mark('epoch %d done' % epoch_num)
-                engine.check()  # errors the training kernels can only report through the ctx
-
-                if verbose:
-                    print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-                if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                    # the reference stops here having consumed the stream up to this epoch's negatives only
-                    raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
-        finally:
-            try:
-                try:
-                    if pingponged:
-                        pingpong.__exit__(None, None, None)  # the rows whose current copy is the ctx's back into torch's tensor
-                finally:
-                    if shadowed:
-                        shadow.__exit__(None, None, None)  # the trained biases and their accumulator back into torch's tensors
-            finally:  # (whatever the write-back raised, the threads are joined and the RandomState is the reference's)
-                if job is not None:
-                    try:
-                        job.join()
-                    except BaseException:  # noqa: BLE001 -- the exception already on its way out wins
-                        pass
-                upload.result()  # (joins the upload thread on the exceptional paths too)
-                check.join()
-                self._random_state.set_state(consumed)
-                # a chunk prepared ahead for an epoch that will not run (an exception left the loop): its draws are dropped and the
-                # ctx's stream is put back where the reference's would be, so that the next training call on this engine -- any
-                # model's -- finds no stale prefetch (slk_bilinear_train would refuse it once)
-                if _PREFETCH and engine.get_stat('prefetch_pending'):
-                    engine.rng_set_state(consumed)
-                # the epoch's device buffers go back to the caching allocator NOW (closures above hold cells, not tensors, once
-                # these names are cleared): the next fit() reuses them instead of allocating
-                del bufs[:]
-                d_perm = d_pairs = unpacked = None
-                upload._out = None
-
-    def _fit_pipelined(self, binding, engine, device, stream, tables, d_users0, d_items0, n, nn, mb_loss, verbose):
-        """The epoch loop for datasets of the reference's own scale (MovieLens-100K: 80 000 interactions per epoch): there an
-        epoch trains in about a millisecond and the numpy-exact device shuffle -- a chain of small launches and read-backs --
-        costs as much again.  The RandomState stream is consumed in the reference's order (shuffle of epoch e, negatives of
-        epoch e, shuffle of epoch e + 1, ...), but nothing in training touches it, so epoch e + 1's shuffle and negatives are
-        drawn on a second slk_ctx / HIP stream while epoch e trains from its own (already drawn) negatives.  Same ids, same
-        negatives, same RandomState afterwards, bit-identical tables; only the wall time changes."""
-        prep, prep_stream = _prep_lane_for(device)
-        torch.cuda.current_stream(device).synchronize() if device.type == 'cuda' else None  # the id upload is complete
-        bufs = [(torch.empty_like(d_users0), torch.empty_like(d_items0),
-                 torch.empty(n * nn, dtype=torch.int64, device=device)) for _ in range(2)]
-        d_perm = torch.empty(n, dtype=torch.int64, device=device)
-
-        def prepare(slot):
-            # shuffle, then the negatives: one MT19937 stream, consumed on the GPU exactly as numpy would consume it
-            prep.rng_set_state(self._random_state.get_state())
-            d_users, d_items, d_neg = bufs[slot]
-            device_epoch_shuffle(prep, self._random_state, n, d_perm, [(d_users0, d_users, 1), (d_items0, d_items, 1)],
-                                 prep_stream)
-            # one randint per minibatch == one contiguous draw over the epoch (sampling.py:34)
-            prep.sample_items(self._num_items, n * nn, d_neg.data_ptr(), stream=prep_stream)
-            self._random_state.set_state(prep.rng_get_state())  # synchronises the prep stream
-
-        prepare(0)
-        for epoch_num in range(self._n_iter):
-            d_users, d_items, d_neg = bufs[epoch_num % 2]
-            ostruct = binding.as_struct()
-            engine.bilinear_train(tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), n, self._batch_size, self._loss,
-                                  self._num_negative_samples, mb_loss.data_ptr(), d_neg_in=d_neg.data_ptr(), stream=stream)
-            binding.store_steps(ostruct.step)
-            state_after_epoch = self._random_state.get_state()
-            if epoch_num + 1 < self._n_iter:
-                prepare((epoch_num + 1) % 2)  # overlaps the training kernels of this epoch
-
-            epoch_loss = float(mb_loss.double().mean().item())  # also waits for this epoch's kernels
-            engine.check()  # errors the training kernels can only report through the ctx (e.g. an abandoned launch)
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                # the reference stops here having consumed the stream up to this epoch's negatives only
-                self._random_state.set_state(state_after_epoch)
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+            job.own_slots(IdUpload([user_ids, item_ids], device).result(), nn)
+            return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
+        threaded = _PREFETCH and lane[0] is not engine and engine._lib is _native._LIB  # (the test harness's emulator is single-threaded)
+        ids = _epochs.ShuffledIds(lane[0], lane[1], user_ids, item_ids, min(self._n_iter, 3 if _PREFETCH else 2), device)
+        job.slots = ids.bufs
+        job.scopes = [
+            engine.bias_shadow(tables, binding.as_struct(), stream=stream,
+                               enabled=(binding.kind == 'adagrad' and self._num_items >= _BIAS_SHADOW_MIN_ITEMS and
+                                        self._batch_size >= 4096 and not tables.item_bloom)),
+            engine.user_pingpong(tables, binding.as_struct(), stream=stream,
+                                 enabled=(self._loss in ('pointwise', 'bpr', 'hinge') and binding.kind in ('adagrad', 'sparse_adam', 'sgd')
+                                          and min(self._batch_size, n) >= _USER_PINGPONG_MIN_BATCH
+                                          and not tables.user_bloom and not tables.item_bloom))]
+        return _epochs.run_three_stage(engine, stream, self._random_state, self._n_iter, verbose, job, ids, check,
+                                       prefetch=_PREFETCH, threaded=threaded)
 
     def _fit_autograd(self, user_ids, item_ids, verbose):
         """The reference's epoch / minibatch loop (implicit.py:208-252, 254-275) for models without a fused path: host numpy
@@ -754,10 +468,7 @@ class ImplicitFactorizationModel(object):
                 self._optimizer.step()
                 n_mb += 1
             epoch_loss /= n_mb
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+            _epochs.end_epoch(epoch_num, epoch_loss, verbose)
 
     def predict(self, user_ids, item_ids=None):
         """Scores for one user against all/some items, or for explicit (user, item) pairs;

@@ -24,7 +24,7 @@ the host side: buffers, split sizes and the collectives (torch.distributed = RCC
 import torch
 import torch.distributed as dist
 
-from spotlight_amd import _native
+from spotlight_amd import _epochs, _native
 
 
 def local_rows(num_rows, world, rank):
@@ -452,11 +452,7 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
                                                        n_neg=nn if adaptive else None, mb_pos=pos[a:b] if adaptive else None))
             dist.all_reduce(mb_loss, group=self._group)
             binding.store_steps(ostruct.step)
-            epoch_loss = float(mb_loss.double().mean().item())
-            if verbose and rank == 0:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+            _epochs.end_epoch(epoch_num, _epochs.mean_loss(mb_loss), verbose and rank == 0)
 
     def _fetch_rows(self, t_emb, t_bias, ids, device):
         """[len(ids), D + 1]: embedding row and bias of every id, assembled from the owners."""

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.optim as optim
 
-from spotlight_amd import _native
+from spotlight_amd import _epochs, _native
 from spotlight_amd.factorization import implicit as _host
 from spotlight_amd.factorization.implicit import _OptimizerBinding
 from spotlight_amd.helpers import _repr_model
@@ -33,6 +33,46 @@ class _SeqOptimizerBinding(_OptimizerBinding):
         slot = lambda xs: [None, xs[0].data_ptr(), None, xs[1].data_ptr()]
         return _native.make_optim(self.kind, slot(self.s1) if self.s1 else None, slot(self.s2) if self.s2 else None,
                                   step=self.steps_taken(), **self.hp)
+
+
+class _SequenceEpochs(object):
+    """What the schedules of spotlight_amd/_epochs.py ask of the fused (PoolNet) sequence model: the composed shuffle and
+    slk_poolnet_reserve / _train.  `draws_ahead`: negatives per sequence element that prepare() draws for the training call
+    (the two-lane schedule), 0 where the call draws its own (serial)."""
+
+    def __init__(self, model, binding, tables, shape, draws_ahead, device):
+        self.binding, self.tables, self.device, self.model = binding, tables, device, model
+        self.n_seq, self.seq_len = shape
+        self.call = (self.n_seq, self.seq_len, model._batch_size, model._loss, model._num_negative_samples)
+        self.mb_loss = torch.empty((self.n_seq + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
+        self.draws = self.n_seq * self.seq_len * draws_ahead
+        self.bufs = self.negs = self.d_perm = None
+
+    def reserve(self, engine, stream):
+        engine.poolnet_reserve(self.tables, self.binding.as_struct(), *self.call, stream=stream)
+
+    def upload(self, sequences):
+        # the sequences go to the device once; `sequences` is rebound to its shuffled copy every epoch, so successive epochs'
+        # permutations compose exactly as in the reference (:215-216) -- here by gathering epoch e's array (bufs[(e + 1) % 2])
+        # from the previous epoch's (bufs[e % 2]: this epoch's source, free again once the NEXT epoch has been gathered from
+        # this one's) with a numpy-exact device permutation
+        d_first = _host.ids_to_device(sequences, self.device)
+        self.bufs = [d_first, torch.empty_like(d_first)]
+        self.d_perm = torch.empty(self.n_seq, dtype=torch.int64, device=self.device)
+        self.negs = [torch.empty(self.draws, dtype=torch.int64, device=self.device) for _ in range(2 if self.draws else 0)]
+
+    def prepare(self, engine, stream, random_state, epoch_num):
+        _epochs.device_epoch_shuffle(engine, random_state, self.n_seq, self.d_perm,
+                                     [(self.bufs[epoch_num % 2], self.bufs[(epoch_num + 1) % 2], self.seq_len)], stream)
+        if self.draws:
+            engine.sample_items(self.model._num_items, self.draws, self.negs[epoch_num % 2].data_ptr(), stream=stream)
+
+    def train(self, engine, stream, epoch_num):
+        ostruct = self.binding.as_struct()
+        engine.poolnet_train(self.tables, ostruct, self.model._padding_idx(), self.bufs[(epoch_num + 1) % 2].data_ptr(), *self.call,
+                             self.mb_loss.data_ptr(), d_neg_in=self.negs[epoch_num % 2].data_ptr() if self.draws else None,
+                             stream=stream)
+        self.binding.store_steps(ostruct.step)
 
 
 class ImplicitSequenceModel(object):
@@ -163,80 +203,18 @@ class ImplicitSequenceModel(object):
         device = self._net.tables()[0].device
         engine = _host._engine_for(device)
         stream = _host._stream_for(device)
-        tables = self._slk_tables()
-        n_seq, seq_len = sequences.shape
-        n_minibatches = (n_seq + self._batch_size - 1) // self._batch_size
-        mb_loss = torch.empty(n_minibatches, dtype=torch.float32, device=device)
-
-        engine.poolnet_reserve(tables, binding.as_struct(), n_seq, seq_len, self._batch_size, self._loss,
-                               self._num_negative_samples, stream=stream)
-        # the sequences go to the device once; `sequences` is rebound to its shuffled copy every epoch,
-        # so successive epochs' permutations compose exactly as in the reference (:215-216) -- here by
-        # gathering from the previous epoch's device array with a numpy-exact device permutation
-        d_prev = _host.ids_to_device(sequences, device)
-        d_sequences = torch.empty_like(d_prev)
-        d_perm = torch.empty(n_seq, dtype=torch.int64, device=device)
         nn = self._num_negative_samples if self._loss == 'adaptive_hinge' else 1
-        if self._n_iter > 1 and n_seq * seq_len * nn <= _host._PIPELINE_MAX_DRAWS:
-            return self._fit_pipelined(binding, engine, device, stream, tables, d_prev, d_sequences, d_perm, n_seq, seq_len, nn,
-                                       mb_loss, verbose)
-        for epoch_num in range(self._n_iter):
-            engine.rng_set_state(self._random_state.get_state())
-            _host.device_epoch_shuffle(engine, self._random_state, n_seq, d_perm, [(d_prev, d_sequences, seq_len)],
-                                       stream)
-            ostruct = binding.as_struct()
-            engine.poolnet_train(tables, ostruct, self._padding_idx(), d_sequences.data_ptr(), n_seq, seq_len,
-                                 self._batch_size, self._loss, self._num_negative_samples,
-                                 mb_loss.data_ptr(), stream=stream)
-            d_prev, d_sequences = d_sequences, d_prev
-            binding.store_steps(ostruct.step)
-            self._random_state.set_state(engine.rng_get_state())  # synchronises the stream
-
-            epoch_loss = float(mb_loss.double().mean().item())
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
-
-    def _fit_pipelined(self, binding, engine, device, stream, tables, d_prev, d_sequences, d_perm, n_seq, seq_len, nn, mb_loss,
-                       verbose):
-        """Small datasets (see ImplicitFactorizationModel._fit_pipelined): epoch e + 1's shuffle (composed with epoch e's, as
-        the reference's rebinding of `sequences` does) and negatives are drawn on a second slk_ctx / HIP stream while epoch e
-        trains from its own, already drawn negatives.  Same sequences, negatives, RandomState and tables, bit for bit."""
-        prep, prep_stream = _host._prep_lane_for(device)
-        torch.cuda.current_stream(device).synchronize() if device.type == 'cuda' else None  # the upload is complete
-        negs = [torch.empty(n_seq * seq_len * nn, dtype=torch.int64, device=device) for _ in range(2)]
-
-        def prepare(src, dst, d_neg):
-            prep.rng_set_state(self._random_state.get_state())
-            _host.device_epoch_shuffle(prep, self._random_state, n_seq, d_perm, [(src, dst, seq_len)], prep_stream)
-            prep.sample_items(self._num_items, n_seq * seq_len * nn, d_neg.data_ptr(), stream=prep_stream)
-            self._random_state.set_state(prep.rng_get_state())  # synchronises the prep stream
-
-        prepare(d_prev, d_sequences, negs[0])
-        for epoch_num in range(self._n_iter):
-            ostruct = binding.as_struct()
-            engine.poolnet_train(tables, ostruct, self._padding_idx(), d_sequences.data_ptr(), n_seq, seq_len,
-                                 self._batch_size, self._loss, self._num_negative_samples, mb_loss.data_ptr(),
-                                 d_neg_in=negs[epoch_num % 2].data_ptr(), stream=stream)
-            binding.store_steps(ostruct.step)
-            state_after_epoch = self._random_state.get_state()
-            if epoch_num + 1 < self._n_iter:
-                # this epoch's (shuffled) sequences are the source of the next permutation; its previous source is free
-                prepare(d_sequences, d_prev, negs[(epoch_num + 1) % 2])
-            d_prev, d_sequences = d_sequences, d_prev
-
-            epoch_loss = float(mb_loss.double().mean().item())  # also waits for this epoch's kernels
-            engine.check()
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                self._random_state.set_state(state_after_epoch)
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+        ahead = self._n_iter > 1 and sequences.size * nn <= _host._PIPELINE_MAX_DRAWS
+        job = _SequenceEpochs(self, binding, self._slk_tables(), sequences.shape, nn if ahead else 0, device)
+        job.reserve(engine, stream)
+        job.upload(sequences)
+        # Small datasets: epoch e + 1's shuffle (composed with epoch e's) and negatives are drawn on a second slk_ctx / HIP
+        # stream while epoch e trains from its own, already drawn negatives (_epochs.run_two_lane).  Same sequences, negatives,
+        # RandomState and tables as the serial loop, bit for bit.
+        if ahead:
+            return _epochs.run_two_lane(engine, stream, _host._prep_lane_for(device), self._random_state, self._n_iter, verbose,
+                                        job, device)
+        return _epochs.run_serial(engine, stream, self._random_state, self._n_iter, verbose, job)
 
     def _fit_autograd(self, sequences, verbose):
         """The reference's epoch loop (sequence/implicit.py:213-264) for encoders whose body is a torch
@@ -279,13 +257,7 @@ class ImplicitSequenceModel(object):
                 self._optimizer.step()
             d_prev, d_sequences = d_sequences, d_prev
             self._random_state.set_state(engine.rng_get_state())  # synchronises the stream
-            epoch_loss = float(torch.stack(losses).double().mean().item())
-
-            if verbose:
-                print('Epoch {}: loss {}'.format(epoch_num, epoch_loss))
-
-            if np.isnan(epoch_loss) or epoch_loss == 0.0:
-                raise ValueError('Degenerate epoch loss: {}'.format(epoch_loss))
+            _epochs.end_epoch(epoch_num, _epochs.mean_loss(torch.stack(losses)), verbose)
 
     def _predict_autograd_free(self, sequences, item_ids):
         """predict() for the torch-side encoders (sequence/implicit.py:322-340)."""

@@ -311,3 +311,19 @@ def test_pipelined_seq_fit_is_value_neutral_on_gpu():
 def test_pipelined_explicit_fit_is_value_neutral_on_gpu():
     from test_host_explicit_model import check_pipelined_explicit_fit_is_value_neutral
     check_pipelined_explicit_fit_is_value_neutral(use_cuda=True, to_numpy=lambda w: w.detach().cpu().numpy())
+
+
+def test_failed_epoch_leaves_the_reference_random_state_on_gpu():
+    """An exception in epoch 0 (a degenerate loss; a failing engine.check()) leaves the RandomState where the reference holds
+    it, on every schedule of the three fused models -- with real streams and the shuffle worker thread beside the passes."""
+    from test_host_explicit_model import check_failed_explicit_epoch_leaves_the_reference_random_state
+    from test_host_model import check_failed_implicit_epoch_leaves_the_reference_random_state
+    from test_host_seq_model import check_failed_seq_epoch_leaves_the_reference_random_state
+    check_failed_implicit_epoch_leaves_the_reference_random_state(use_cuda=True)
+    check_failed_explicit_epoch_leaves_the_reference_random_state(use_cuda=True)
+    check_failed_seq_epoch_leaves_the_reference_random_state(use_cuda=True)
+
+
+def test_scope_that_fails_to_open_closes_the_one_before_it_on_gpu():
+    from test_host_model import check_scope_that_fails_to_open_closes_the_one_before_it
+    check_scope_that_fails_to_open_closes_the_one_before_it(use_cuda=True, to_numpy=lambda w: w.detach().cpu().numpy())

@@ -72,7 +72,7 @@ def test_fit_predict_match_reference_run(emu_device, name):
 
 
 def check_pipelined_explicit_fit_is_value_neutral(use_cuda=False, to_numpy=lambda w: w.detach().numpy()):
-    """fit() of a small dataset shuffles epoch e + 1 while epoch e trains (ExplicitFactorizationModel._fit_pipelined); the
+    """fit() of a small dataset shuffles epoch e + 1 while epoch e trains (spotlight_amd/_epochs.py: run_two_lane); the
     serial loop it replaces must give the same tables and RandomState, bit for bit."""
     rs = np.random.RandomState(12)
     inter = Interactions(rs.randint(0, 90, 2000).astype(np.int32), rs.randint(0, 60, 2000).astype(np.int32),
@@ -100,6 +100,24 @@ def check_pipelined_explicit_fit_is_value_neutral(use_cuda=False, to_numpy=lambd
 
 def test_pipelined_explicit_fit_is_value_neutral(emu_device):
     check_pipelined_explicit_fit_is_value_neutral()
+
+
+def check_failed_explicit_epoch_leaves_the_reference_random_state(use_cuda=False, to_numpy=None):
+    """tests/test_host_model.py: check_failed_epoch_leaves_the_reference_random_state for the explicit-feedback model, which
+    draws no negatives: the reference holds the stream behind epoch 0's shuffle."""
+    from test_host_model import _poison_row, check_failed_epoch_leaves_the_reference_random_state
+    rs = np.random.RandomState(12)
+    inter = Interactions(rs.randint(0, 90, 2000).astype(np.int32), rs.randint(0, 60, 2000).astype(np.int32),
+                         ratings=rs.randint(1, 6, 2000).astype(np.float32), num_users=90, num_items=60)
+    check_failed_epoch_leaves_the_reference_random_state(
+        lambda n_iter: ExplicitFactorizationModel(loss='regression', embedding_dim=8, n_iter=n_iter, batch_size=256, optimizer_func=_adagrad,
+                                                  use_cuda=use_cuda, random_state=np.random.RandomState(7)),
+        inter, lambda ref: ref.shuffle(np.arange(2000)), lambda model: _poison_row(model._net.tables()[0], int(inter.user_ids[0])),
+        serial_at_zero=True, use_cuda=use_cuda)
+
+
+def test_failed_explicit_epoch_leaves_the_reference_random_state(emu_device):
+    check_failed_explicit_epoch_leaves_the_reference_random_state()
 
 
 def test_errors(emu_device):

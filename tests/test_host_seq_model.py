@@ -190,7 +190,7 @@ def test_to_sequence_device_route(emu_device):
 
 
 def check_pipelined_seq_fit_is_value_neutral(use_cuda=False, to_numpy=lambda w: w.detach().numpy()):
-    """ImplicitSequenceModel._fit_pipelined (next epoch's composed shuffle + negatives drawn while this epoch trains) against
+    """ImplicitSequenceModel under spotlight_amd/_epochs.py: run_two_lane (next epoch's composed shuffle + negatives drawn while this epoch trains) against
     the serial epoch loop: tables and RandomState bit for bit."""
     from spotlight_amd.factorization import implicit as host_mod
     from spotlight_amd.interactions import SequenceInteractions
@@ -220,3 +220,26 @@ def check_pipelined_seq_fit_is_value_neutral(use_cuda=False, to_numpy=lambda w: 
 
 def test_pipelined_seq_fit_is_value_neutral(emu_device):
     check_pipelined_seq_fit_is_value_neutral()
+
+
+def check_failed_seq_epoch_leaves_the_reference_random_state(use_cuda=False, to_numpy=None):
+    """tests/test_host_model.py: check_failed_epoch_leaves_the_reference_random_state for the pooling sequence model: one
+    shuffle of the sequences and one draw per sequence element an epoch; the NaN goes into an item row."""
+    from test_host_model import _poison_row, check_failed_epoch_leaves_the_reference_random_state
+    rs = np.random.RandomState(5)
+    seqs = rs.randint(1, 80, (150, 12)).astype(np.int32)
+    seqs[rs.rand(150) < 0.4, :4] = 0
+    data = SequenceInteractions(seqs, num_items=80)
+
+    def replay_epoch(ref):
+        ref.shuffle(np.arange(150))
+        ref.randint(0, 80, 150 * 12, dtype=np.int64)
+    check_failed_epoch_leaves_the_reference_random_state(
+        lambda n_iter: ImplicitSequenceModel(loss='bpr', representation='pooling', embedding_dim=8, n_iter=n_iter, batch_size=64,
+                                             optimizer_func=_adagrad, use_cuda=use_cuda, random_state=np.random.RandomState(7)),
+        data, replay_epoch, lambda model: _poison_row(model._net.tables()[0], int(seqs[0, -1])), serial_at_zero=True,
+        use_cuda=use_cuda)
+
+
+def test_failed_seq_epoch_leaves_the_reference_random_state(emu_device):
+    check_failed_seq_epoch_leaves_the_reference_random_state()
