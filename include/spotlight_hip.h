@@ -220,7 +220,11 @@ int slk_ctx_get_option(slk_ctx *ctx, const char *name, int64_t *value);
  * "pingpong_calls" (slk_bilinear_train calls that ran on the user-row ping-pong of slk_user_pingpong_begin),
  * "single_minibatches" (minibatches whose once-only items were updated by the user pass: option "item_single_min_items"),
  * "prefetch_pending" (what the last slk_bilinear_prefetch left for the next training call: 0 nothing -- it was a no-op --,
- * 1 the first chunk, 2 the first chunk and the negatives of the whole call). */
+ * 1 the first chunk, 2 the first chunk and the negatives of the whole call),
+ * "sort_finish_cap" (pairs a bucket of the radix sort's top-digit route may hold: csrc/slk_sort.hip),
+ * "sort_finish_sorts" (sorts enqueued on that route since the ctx was created),
+ * "sort_finish_fallbacks" (those of them whose buckets did not fit -- skewed ids -- and which the LSD passes sorted instead;
+ * counted on the device: the call waits for the device's outstanding work and copies the counter). */
 int slk_ctx_get_stat(slk_ctx *ctx, const char *name, int64_t *value);
 
 /* numpy RandomState.set_state()/get_state() hand-over of the MT19937 stream the reference

@@ -304,6 +304,16 @@ SLK_EXPORT int slk_ctx_get_stat(slk_ctx *ctx, const char *name, int64_t *value) 
     else if (!strcmp(name, "lds_per_block")) *value = (int64_t)ctx->lds_per_block;
     else if (!strcmp(name, "lds_per_cu")) *value = (int64_t)ctx->lds_per_cu;
     else if (!strcmp(name, "prefetch_pending")) *value = !ctx->pf.valid ? 0 : (ctx->pf.all ? 2 : 1);
+    else if (!strcmp(name, "sort_finish_cap")) *value = slk_sort_finish_cap();
+    else if (!strcmp(name, "sort_finish_sorts")) *value = ctx->stat_sort_finish_sorts;
+    else if (!strcmp(name, "sort_finish_fallbacks")) {
+        // counted on the device (the host never learns inside a sort whether its buckets fitted): wait for the sorts, then copy
+        uint32_t h = 0;
+        SLK_HIP(ctx, hipSetDevice(ctx->device));
+        SLK_HIP(ctx, hipDeviceSynchronize());
+        SLK_HIP(ctx, hipMemcpy(&h, &ctx->d_rng->sort_fallbacks, sizeof(h), hipMemcpyDeviceToHost));
+        *value = (int64_t)h;
+    }
     else return slk_fail(ctx, SLK_EINVAL, "slk_ctx_get_stat: unknown statistic %s", name);
     return SLK_OK;
 }

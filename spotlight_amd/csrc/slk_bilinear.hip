@@ -1510,11 +1510,13 @@ static int prep_sort(slk_ctx *ctx, const train_plan &p, const train_call &c, con
     if (!p.pre) {
         // (keys and the fat (positive, negative) payload are formed by the sort's first pass from the id arrays)
         uint64_t *const uvals[2] = {(uint64_t *)pb.uval[0].p, (uint64_t *)pb.uval[1].p};
-        if ((rc = slk_sort_user_fat(ctx, cu, ci, neg32, nc, (size_t)bsz, p.ubits, mbbits, ukeys, uvals, s))) return rc;
+        if ((rc = slk_sort_user_fat(ctx, cu, ci, neg32, nc, (size_t)bsz, p.ubits, mbbits, (size_t)c.tables->num_users, ukeys, uvals,
+                                    s)))
+            return rc;
         uit = u32p(pb.uval[1]);  // little-endian (pos, neg) pairs
     } else {
         uint32_t *const uvals[2] = {u32p(pb.uval[0]), u32p(pb.uval[1])};
-        if ((rc = slk_sort_user_idx(ctx, cu, nc, (size_t)bsz, p.ubits, mbbits, ukeys, uvals, s))) return rc;
+        if ((rc = slk_sort_user_idx(ctx, cu, nc, (size_t)bsz, p.ubits, mbbits, (size_t)c.tables->num_users, ukeys, uvals, s))) return rc;
         uk = u32p(pb.uval[1]);
         hipLaunchKernelGGL(k_pack_items, dim3(slk_grid_for(ctx, nc, 256)), dim3(256), 0, s, uk, ci, neg32, nc, p.nn, u32p(pb.uit));
         SLK_LAUNCH_CHECK(ctx, "k_pack_items");
@@ -1526,7 +1528,8 @@ static int prep_sort(slk_ctx *ctx, const train_plan &p, const train_call &c, con
     } else {
         uint32_t *const ikeys[2] = {u32p(pb.ikey[0]), u32p(pb.ikey[1])};
         uint32_t *const ivals[2] = {u32p(pb.ipay[0]), u32p(pb.ipay[1])};
-        if ((rc = slk_sort_item_occ(ctx, uit, nocc, (size_t)bsz, p.NP, p.ibits, mbbits, ikeys, ivals, s))) return rc;
+        if ((rc = slk_sort_item_occ(ctx, uit, nocc, (size_t)bsz, p.NP, p.ibits, mbbits, (size_t)c.tables->num_items, ikeys, ivals, s)))
+            return rc;
         if (p.sgl_on && (rc = prep_single_flags(ctx, p, c, pb, ck, s))) return rc;
     }
     // which minibatches hold a LONG run (an item run that wholly covers a tile of the item pass, [0, n_mb); a user run that

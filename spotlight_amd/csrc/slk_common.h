@@ -84,6 +84,8 @@ struct slk_rng_dev {
     unsigned long long accepted;
     int32_t epoch_abort;      // sticky: the persistent epoch kernel abandoned a launch (grid barrier time-out)
     int32_t sort_abort;       // sticky: a radix-sort look-back gave up waiting for the tile before it (slk_sort.hip)
+    uint32_t sort_fallbacks;  // sorts on the top-digit route whose buckets did not fit the finish: the LSD passes sorted them
+    uint32_t pad_;
 };
 
 #define SLK_EXTRA_BUFS 56
@@ -288,6 +290,7 @@ struct slk_ctx {
     int64_t stat_shadowed = 0;      // training calls that ran on the item-bias shadow (slk_bias_shadow_begin)
     int64_t stat_pingpong = 0;      // training calls that ran on the user-row ping-pong (slk_user_pingpong_begin)
     int64_t stat_single = 0;        // minibatches whose once-only items were updated by the user pass (k_user_pass<..., SGL>)
+    int64_t stat_sort_finish_sorts = 0;  // sorts enqueued on the top-digit route (slk_sort.hip)
     int last_pipe_set = -1;         // buffer set of the last chunk of the last pipelined training call (-1: none yet)
     uint32_t ipart_gen = 0;         // item pass: stamp of the last launch's partials (slk_launch_item_pass)
     uint32_t upart_gen = 0;         // user pass, long runs: likewise (slk_bilinear.hip)
@@ -386,13 +389,14 @@ int slk_sort_fy_steps(slk_ctx *ctx, slk_buf &scratch, const uint32_t *J, uint32_
 int slk_sort_pairs_any(slk_ctx *ctx, int kind, const void *kin, void *kout, const void *vin, void *vout, size_t n, size_t seg_len,
                        unsigned bits, hipStream_t s, bool clobber);
 // the training prep's sorts: keys built by the first pass from the id arrays, one segment per minibatch of `bsz` interactions;
-// result in (key[1], val[1]), (key[0], val[0]) is the second buffer pair
+// result in (key[1], val[1]), (key[0], val[0]) is the second buffer pair.  num_users / num_items: the ids are below it (sizes
+// the buckets of the sort's top-digit route, slk_sort.hip)
 int slk_sort_user_fat(slk_ctx *ctx, const int64_t *users, const int64_t *items, const uint32_t *neg32, size_t nc, size_t bsz,
-                      unsigned ubits, unsigned mbbits, uint32_t *const key[2], uint64_t *const val[2], hipStream_t s);
-int slk_sort_user_idx(slk_ctx *ctx, const int64_t *users, size_t nc, size_t bsz, unsigned ubits, unsigned mbbits,
+                      unsigned ubits, unsigned mbbits, size_t num_users, uint32_t *const key[2], uint64_t *const val[2], hipStream_t s);
+int slk_sort_user_idx(slk_ctx *ctx, const int64_t *users, size_t nc, size_t bsz, unsigned ubits, unsigned mbbits, size_t num_users,
                       uint32_t *const key[2], uint32_t *const val[2], hipStream_t s);
 int slk_sort_item_occ(slk_ctx *ctx, const uint32_t *uit, size_t nocc, size_t bsz, int NP, unsigned ibits, unsigned mbbits,
-                      uint32_t *const key[2], uint32_t *const val[2], hipStream_t s);
+                      size_t num_items, uint32_t *const key[2], uint32_t *const val[2], hipStream_t s);
 
 // slk_eval.hip: one representation against every item through the GEMM sweep (predict with d_items == NULL)
 int slk_eval_predict_all(slk_ctx *ctx, const slk_tables *tables, const float *rep, const float *rbias, const int64_t *gmap,
@@ -409,6 +413,7 @@ int slk_check_tables(slk_ctx *ctx, const slk_tables *t, unsigned table_mask, int
 int slk_launch_i64_to_u32(slk_ctx *ctx, const int64_t *in, uint32_t *out, size_t n, hipStream_t s);
 
 int slk_sort_reserve(slk_ctx *ctx, size_t n);
+int64_t slk_sort_finish_cap(void);  // pairs a bucket of the top-digit route may hold (slk_ctx_get_stat "sort_finish_cap")
 // positions where a sorted key array changes value -> d_heads[0..nseg), d_heads[nseg] = n; optionally the
 // segment index of every position -> d_segid[n] (slk_seqprep.hip).  Synchronises the stream (nseg is
 // returned to the host).

@@ -20,6 +20,17 @@
 // (tile, digit) (sc1 stores / loads: the producer may sit on another XCD), exchanges keys then payloads through LDS so that
 // every (tile, bucket) run leaves as consecutive lanes, and writes.  HBM-bound: 8 B (u32 payload) / 12 B (u64) read + written
 // per pair and pass, + 4 B for the histogram.
+//
+// A second route, for the training prep's large segmented sorts of u32 keys (segments of >= RS_FIN_MIN_SEG pairs, more than 8
+// key bits): TWO global passes instead of three.  A per-tile count of the TOP digit (k_rs_tile_hist), a prefix over each
+// segment's tiles (k_rs_tile_scan, k_rs_bucket_base), ONE scatter on the top digit that reads "pairs before this tile" from that
+// table (k_rs_scatter<TOP>: no ticket, no status word, no look-back), then one workgroup per (segment, bucket) sorts its bucket
+// on the remaining bits in registers + LDS and writes it out in full lines (k_rs_finish).  The top digit's width is chosen on
+// the host from the segment length and the id range (rs_pick_topw) so that a bucket stays under RS_FIN_CAP pairs; whether every
+// bucket did is decided on the device (`nofit`): if not -- skewed ids -- these kernels return at once and the LSD kernels, always
+// enqueued behind them, sort; otherwise those return at once.  Nothing on this route waits for another workgroup.
+#include <math.h>
+
 #include "slk_common.h"
 
 namespace {
@@ -54,6 +65,13 @@ struct rs_args {
     int xcd;                 // 1: a segment's tiles are taken by the workgroups of ONE XCD (segment s -> XCD s % 8)
     uint32_t nseg;
     int debug;               // measurement only (option "sort_debug"): 1 no look-back walk, 2 ranks from LDS atomics
+    // the top-digit route (below): one scatter on the key bits [topshift, topshift + topw), then a finish per bucket
+    int topw, topshift;
+    uint32_t *tpre;          // [tile][1 << topw]: the tile's top-digit counts, then those of the segment's tiles before it
+    uint32_t *btot, *bbase;  // [segment][RS_RADIX]: pairs of the bucket / its first output position
+    uint32_t *nofit;         // one word per sort: != 0 when a bucket holds more than RS_FIN_CAP pairs (the LSD passes run instead)
+    uint32_t *fallbacks;     // slk_rng_dev::sort_fallbacks: sorts whose nofit came out != 0
+    int gate;                // LSD kernels enqueued behind the top-digit route: return at once unless *nofit
 };
 
 template <class KeyT>
@@ -106,6 +124,7 @@ __device__ __forceinline__ KeyT rs_load_key(const rs_args &a, uint32_t gi, uint3
 template <class KeyT, int LOADER>
 __global__ __launch_bounds__(256) void k_rs_hist(rs_args a) {
     __shared__ uint32_t sh[RS_MAX_PASS * RS_RADIX];
+    if (a.gate && !*a.nofit) return;  // (the top-digit route sorted it)
     const uint32_t seg = blockIdx.x / a.hbps, hb = blockIdx.x - seg * a.hbps;
     const uint32_t s0 = seg * a.seg_len;
     const uint32_t s1 = (a.n - s0 < a.seg_len) ? a.n : s0 + a.seg_len;
@@ -158,6 +177,7 @@ __device__ __forceinline__ uint32_t rs_block_excl_scan(uint32_t v, uint32_t *s_w
 // bucket bases: base[segment][pass][d] = segment start + (pairs of the segment whose digit is < d)
 __global__ __launch_bounds__(256) void k_rs_scan(rs_args a) {
     __shared__ uint32_t s_wsum[4];
+    if (a.gate && !*a.nofit) return;
     const uint32_t seg = blockIdx.x / (uint32_t)a.npass;
     const size_t o = (size_t)blockIdx.x * RS_RADIX + threadIdx.x;
     const uint32_t c = a.hist[o];
@@ -224,7 +244,9 @@ __device__ __forceinline__ bool rs_walk(const rs_args &a, const uint32_t *row0, 
 // lane and forms the bucket offsets while the other seven rank -- was built and measured in round 4: 0.235 / 0.314 ms against
 // 0.227 / 0.304 ms for the C2 user / item sorts without it, profiles/r04_l_*.  The walk of the FIRST wave of tiles is a chain
 // through the tiles before them whoever walks it; the tiles behind find inclusive counts at once.  Removed.)
-template <class KeyT, class ValT, int THREADS, int KPT, int LOADER, bool SINGLE>
+// TOP: the top-digit route's scatter (below): the tile is the workgroup's index and the counts of the tiles before it come from
+// the table k_rs_tile_scan wrote -- no ticket, no status word, no look-back.
+template <class KeyT, class ValT, int THREADS, int KPT, int LOADER, bool SINGLE, bool TOP = false>
 __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_scatter(rs_args a) {
     constexpr int WAVES = THREADS / 64, KW = WAVES, TILE = KW * 64 * KPT;
     constexpr int OPT = (TILE + THREADS - 1) / THREADS;  // output positions per thread
@@ -238,9 +260,14 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr bool is_key = true;  // (every wave holds keys)
-    const int shift = a.shift[a.pass], nbits = a.width[a.pass];
+    if (TOP) {
+        if (*a.nofit) return;
+    } else if (!SINGLE && a.gate && !*a.nofit) {
+        return;
+    }
+    const int shift = TOP ? a.topshift : a.shift[a.pass], nbits = TOP ? a.topw : a.width[a.pass];
     const uint32_t radix = 1u << nbits, dmask = radix - 1u;
-    if (!SINGLE && threadIdx.x == 0) {
+    if (!SINGLE && !TOP && threadIdx.x == 0) {
         if (a.xcd) {
             // Segment s belongs to XCD s % 8: its tiles' runs meet in ONE L2 (adjacent tiles complete each other's partial lines
             // before they are written back) and its look-back words never cross the fabric.  A workgroup whose XCD has run out
@@ -263,7 +290,7 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
     for (int i = threadIdx.x; i < KW * RS_RADIX; i += THREADS) s_cnt[i] = 0u;
     if (threadIdx.x < RS_RADIX) s_lbase[threadIdx.x] = 0u;
     __syncthreads();
-    const uint32_t tile = SINGLE ? 0u : s_tile;
+    const uint32_t tile = SINGLE ? 0u : (TOP ? blockIdx.x : s_tile);
     if (tile == 0xffffffffu) return;  // (cannot happen: one workgroup per tile)
     const uint32_t seg = tile / a.tps, tis = tile - seg * a.tps;
     const uint32_t s0 = seg * a.seg_len;
@@ -298,7 +325,7 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
             }
         }
         // the tile's digit counts: published BEFORE the ranking, so the tiles behind this one add them up while it ranks
-        if (!SINGLE) {
+        if (!SINGLE && !TOP) {
 #pragma unroll
             for (int j = 0; j < KPT; ++j)
                 if (e0 + (uint32_t)j * 64u < cnt) atomicAdd(&s_lbase[rs_digit<KeyT>(key[j], shift, dmask)], 1u);
@@ -310,7 +337,7 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
             val[j] = 0;
         }
     }
-    if (!SINGLE) __syncthreads();
+    if (!SINGLE && !TOP) __syncthreads();
 
     uint32_t tcount = 0, before = 0;
     uint32_t *wcnt = s_cnt + (is_key ? wave : 0) * RS_RADIX;
@@ -338,7 +365,8 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
     };
     {
         const uint32_t d = threadIdx.x;
-        if (!SINGLE && d < radix) {
+        if (TOP && d < radix) before = a.tpre[(size_t)tile * radix + d];
+        if (!SINGLE && !TOP && d < radix) {
             tcount = s_lbase[d];
             __hip_atomic_store(a.status + (size_t)tile * radix + d, ((tis == 0 ? RS_INC : RS_AGG) << 30) | tcount, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
@@ -360,12 +388,13 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
                 s_cnt[w * RS_RADIX + d] = run;
                 run += c;
             }
-            if (SINGLE) tcount = run;
+            if (SINGLE || TOP) tcount = run;
         }
         const uint32_t lb = rs_block_excl_scan<THREADS>(tcount, s_wsum);
         if (d < radix) {
             uint32_t gbase = lb;
-            if (!SINGLE) gbase = a.base[((size_t)seg * a.npass + a.pass) * RS_RADIX + d];
+            if (TOP) gbase = a.bbase[(size_t)seg * RS_RADIX + d];
+            else if (!SINGLE) gbase = a.base[((size_t)seg * a.npass + a.pass) * RS_RADIX + d];
             s_lbase[d] = lb;
             s_goff[d] = gbase + before - lb;
         }
@@ -411,10 +440,229 @@ __global__ __launch_bounds__(THREADS) SLK_WAVES_PER_EU_RANGE(4, 6) void k_rs_sca
     }
 }
 
+// ---- the top-digit route: ONE global scatter on the top `topw` key bits, then every bucket is finished inside one workgroup ----
+// For the segmented sorts of u32 keys (the training prep): two global passes instead of three, and nothing in them waits for
+// another workgroup.  k_rs_tile_hist counts the top digit per scatter tile -> k_rs_tile_scan turns the counts into "pairs of the
+// segment's tiles before this one" -> k_rs_bucket_base forms the bucket bases and the word `nofit` -> k_rs_scatter<TOP> ->
+// k_rs_finish.  A bucket of more than RS_FIN_CAP pairs (skewed ids) raises `nofit`: scatter and finish return at once and the
+// LSD kernels enqueued behind them do the sort; otherwise those return at once.  The host never reads `nofit`.
+
+// the finish's workgroup: capacity RS_FIN_CAP = threads x keys per thread (9216: the C2 item side's buckets hold 8559 + 6 sigma)
+#ifndef RS_FIN_THREADS
+#define RS_FIN_THREADS 512
+#endif
+#ifndef RS_FIN_KPT
+#define RS_FIN_KPT 18
+#endif
+// Segments shorter than this keep the LSD passes: measured (profiles/r07_a_sort_sweep.md), the route wins at segments of 2^20 /
+// 2^21 pairs, is even at 2^18 and loses at 2^16, where the digit that keeps a bucket under the capacity is narrow and the finish
+// needs three local rounds.  The test hook "sort_big_min" lowers the gate with the tile threshold: min(this, sort_big_min).
+#ifndef RS_FIN_MIN_SEG
+#define RS_FIN_MIN_SEG (1 << 20)
+#endif
+constexpr uint32_t RS_FIN_CAP = (uint32_t)RS_FIN_THREADS * RS_FIN_KPT;
+static_assert(RS_FIN_KPT % 2 == 0 && RS_FIN_THREADS % 64 == 0 && RS_FIN_THREADS >= RS_RADIX && RS_FIN_CAP <= 65536u, "finish tile shape");
+
+// the top digit's counts of one scatter tile, written plainly to tpre[tile][1 << topw]
+template <class KeyT, int LOADER, int THREADS, int KPT>
+__global__ __launch_bounds__(THREADS) void k_rs_tile_hist(rs_args a) {
+    constexpr uint32_t TILE = (uint32_t)THREADS * KPT;
+    __shared__ uint32_t sh[RS_RADIX];
+    const uint32_t tile = blockIdx.x, seg = tile / a.tps, tis = tile - seg * a.tps;
+    const uint32_t s0 = seg * a.seg_len;
+    const uint32_t s1 = (a.n - s0 < a.seg_len) ? a.n : s0 + a.seg_len;
+    const uint32_t t0 = s0 + tis * TILE;
+    const uint32_t cnt = t0 >= s1 ? 0u : ((s1 - t0 < TILE) ? s1 - t0 : TILE);
+    const uint32_t radix = 1u << a.topw, dmask = radix - 1u;
+    for (uint32_t i = threadIdx.x; i < radix; i += THREADS) sh[i] = 0u;
+    __syncthreads();
+    KeyT k[KPT];
+#pragma unroll
+    for (int j = 0; j < KPT; ++j) {
+        const uint32_t e = (uint32_t)j * THREADS + threadIdx.x;
+        k[j] = e < cnt ? rs_load_key<KeyT, LOADER>(a, t0 + e, seg) : (KeyT)0;
+    }
+#pragma unroll
+    for (int j = 0; j < KPT; ++j)
+        if ((uint32_t)j * THREADS + threadIdx.x < cnt) atomicAdd(&sh[rs_digit<KeyT>(k[j], a.topshift, dmask)], 1u);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < radix; i += THREADS) a.tpre[(size_t)tile * radix + i] = sh[i];
+}
+
+// per (segment, digit): tpre[tile][d] -> pairs with digit d in the segment's tiles before `tile`; btot[segment][d] = the bucket's
+// size.  One workgroup per (segment, 32 digits): 32 lanes read one 128-byte line of a tile's row, 8 such groups share the tiles.
+__global__ __launch_bounds__(256) void k_rs_tile_scan(rs_args a) {
+    __shared__ uint32_t s_part[256];
+    const uint32_t radix = 1u << a.topw;
+    const uint32_t dg = radix < 32u ? radix : 32u, ngr = radix / dg, parts = 256u / dg;
+    const uint32_t seg = blockIdx.x / ngr, dl = threadIdx.x % dg, part = threadIdx.x / dg;
+    const uint32_t d = (blockIdx.x - seg * ngr) * dg + dl;
+    const uint32_t tpp = (a.tps + parts - 1u) / parts;
+    const uint32_t ta = part * tpp < a.tps ? part * tpp : a.tps, tb = ta + tpp < a.tps ? ta + tpp : a.tps;
+    uint32_t *col = a.tpre + (size_t)seg * a.tps * radix + d;
+    uint32_t sum = 0;
+#pragma unroll 8
+    for (uint32_t t = ta; t < tb; ++t) sum += col[(size_t)t * radix];
+    s_part[threadIdx.x] = sum;
+    __syncthreads();
+    uint32_t run = 0, tot = 0;
+    for (uint32_t p = 0; p < parts; ++p) {
+        const uint32_t v = s_part[p * dg + dl];
+        if (p < part) run += v;
+        tot += v;
+    }
+    for (uint32_t t = ta; t < tb; t += 8u) {  // (eight loads in flight, then their stores)
+        uint32_t c[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) c[u] = t + u < tb ? col[(size_t)(t + u) * radix] : 0u;
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) {
+            if (t + u < tb) col[(size_t)(t + u) * radix] = run;
+            run += c[u];
+        }
+    }
+    if (part == 0) a.btot[(size_t)seg * RS_RADIX + d] = tot;
+}
+
+// bucket bases of one segment, and the sort's `nofit`
+__global__ __launch_bounds__(256) void k_rs_bucket_base(rs_args a) {
+    __shared__ uint32_t s_wsum[4];
+    __shared__ uint32_t s_over;
+    const uint32_t seg = blockIdx.x, d = threadIdx.x, radix = 1u << a.topw;
+    if (d == 0) s_over = 0u;
+    const uint32_t c = d < radix ? a.btot[(size_t)seg * RS_RADIX + d] : 0u;
+    const uint32_t ex = rs_block_excl_scan<256>(c, s_wsum);
+    if (d < radix) a.bbase[(size_t)seg * RS_RADIX + d] = seg * a.seg_len + ex;
+    if (c > RS_FIN_CAP) atomicOr(&s_over, 1u);
+    __syncthreads();
+    if (d == 0 && s_over && atomicExch(a.nofit, 1u) == 0u) atomicAdd(a.fallbacks, 1u);  // (counted once per sort)
+}
+
+// One workgroup per (segment, bucket): the bucket's pairs (at most RS_FIN_CAP, in the order the scatter left them = input order)
+// are sorted on the key bits below the top digit in ceil(topshift / 8) stable local rounds -- the scatter's ballot ranking,
+// per-wave counters and scan -- and written to the final pair, every wave 64 consecutive pairs at a time.  Keys and payloads stay
+// in registers between rounds and cross the workgroup through ONE 4-byte-per-pair LDS buffer (a u64 payload in two halves), so
+// the capacity is bounded by registers, not LDS: 36 KB exchange + 8 KB counters per workgroup.
+// Occupancy the compiler gives at 512 x 18 (gfx950): u32 payload 93 VGPRs = 5 waves per SIMD, u64 payload 118 VGPRs = 4 waves per
+// SIMD; a workgroup is 2 waves per SIMD, so 2 workgroups per CU on both sides (LDS, 45 KB per workgroup, would allow 3).
+// Measured against 1024 x 10 and 768 x 12 (profiles/r07_a_sort_sweep.md): 512 x 18 is the fastest on the user side and within
+// 6 % of the best on the item side.
+template <class ValT>
+__global__ __launch_bounds__(RS_FIN_THREADS) SLK_WAVES_PER_EU_RANGE(4, 8) void k_rs_finish(rs_args a) {
+    constexpr int THREADS = RS_FIN_THREADS, KPT = RS_FIN_KPT, WAVES = THREADS / 64;
+    __shared__ uint32_t s_cnt[WAVES * RS_RADIX];
+    __shared__ uint32_t s_lbase[RS_RADIX];
+    __shared__ uint32_t s_wsum[WAVES];
+    __shared__ uint32_t s_x[RS_FIN_CAP];
+    if (*a.nofit) return;
+    const uint32_t seg = blockIdx.x >> a.topw, b = blockIdx.x & ((1u << a.topw) - 1u);
+    const uint32_t cnt = a.btot[(size_t)seg * RS_RADIX + b];
+    if (cnt == 0u) return;  // (cnt <= RS_FIN_CAP: nofit is clear)
+    const uint32_t b0 = a.bbase[(size_t)seg * RS_RADIX + b];
+    const uint32_t *kin = (const uint32_t *)a.kin + b0;
+    const ValT *vin = (const ValT *)a.vin + b0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t e0 = (uint32_t)wave * 64u * KPT + (uint32_t)lane;  // element order = wave, round, lane
+    uint32_t key[KPT];
+    ValT val[KPT];
+    uint32_t pos2[KPT / 2];
+#pragma unroll
+    for (int j = 0; j < KPT; ++j) {
+        const uint32_t e = e0 + (uint32_t)j * 64u;
+        key[j] = e < cnt ? kin[e] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < KPT; ++j) {
+        const uint32_t e = e0 + (uint32_t)j * 64u;
+        val[j] = e < cnt ? vin[e] : (ValT)0;
+    }
+    const int rem = a.topshift, R = (rem + RS_RB - 1) / RS_RB, lo = rem / R, extra = rem % R;
+    uint32_t *wcnt = s_cnt + wave * RS_RADIX;
+    int shift = 0;
+    for (int r = 0; r < R; ++r) {
+        const int nbits = lo + (r < extra ? 1 : 0);
+        const uint32_t radix = 1u << nbits, dmask = radix - 1u;
+        for (int i = threadIdx.x; i < WAVES * RS_RADIX; i += THREADS) s_cnt[i] = 0u;
+        __syncthreads();
+        // ranks inside the wave's 64 * KPT elements, in element order
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            if ((j & 1) == 0) pos2[j / 2] = 0u;
+            if ((uint32_t)wave * 64u * KPT + (uint32_t)j * 64u >= cnt) continue;  // (wave-uniform)
+            const bool valid = e0 + (uint32_t)j * 64u < cnt;
+            const uint32_t dj = rs_digit<uint32_t>(key[j], shift, dmask);
+            const unsigned long long m = rs_match(dj, nbits, valid);
+            const int leader = m ? __ffsll((long long)m) - 1 : lane;
+            uint32_t first = 0;
+            if (m && lane == leader) first = atomicAdd(&wcnt[dj], (uint32_t)__popcll(m));
+            first = __shfl(first, leader);
+            const uint32_t rk = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            pos2[j / 2] = (j & 1) ? (pos2[j / 2] | (rk << 16)) : rk;
+        }
+        __syncthreads();
+        // per digit: waves' counts -> the wave's first rank in the bucket of this round; the digit's count -> its first position
+        uint32_t tcount = 0;
+        if (threadIdx.x < radix) {
+            uint32_t run = 0;
+            for (int w = 0; w < WAVES; ++w) {
+                const uint32_t c = s_cnt[w * RS_RADIX + threadIdx.x];
+                s_cnt[w * RS_RADIX + threadIdx.x] = run;
+                run += c;
+            }
+            tcount = run;
+        }
+        const uint32_t lb = rs_block_excl_scan<THREADS>(tcount, s_wsum);
+        if (threadIdx.x < radix) s_lbase[threadIdx.x] = lb;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            if (e0 + (uint32_t)j * 64u < cnt) {
+                const uint32_t dj = rs_digit<uint32_t>(key[j], shift, dmask);
+                const uint32_t pj = ((pos2[j / 2] >> ((j & 1) * 16)) & 0xffffu) + s_lbase[dj] + wcnt[dj];
+                pos2[j / 2] = (j & 1) ? ((pos2[j / 2] & 0xffffu) | (pj << 16)) : ((pos2[j / 2] & 0xffff0000u) | pj);
+                s_x[pj] = key[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < KPT; ++j)
+            if (e0 + (uint32_t)j * 64u < cnt) key[j] = s_x[e0 + (uint32_t)j * 64u];
+        __syncthreads();
+        // the payload behind its key: 32 bits per crossing
+#pragma unroll
+        for (int h = 0; h < (int)(sizeof(ValT) / 4); ++h) {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if (e0 + (uint32_t)j * 64u < cnt)
+                    s_x[(pos2[j / 2] >> ((j & 1) * 16)) & 0xffffu] = (uint32_t)((uint64_t)val[j] >> (32 * h));
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if (e0 + (uint32_t)j * 64u < cnt) {
+                    const uint64_t w32 = s_x[e0 + (uint32_t)j * 64u];
+                    if (sizeof(ValT) == 4) val[j] = (ValT)w32;
+                    else val[j] = (ValT)(h == 0 ? (((uint64_t)val[j] & 0xffffffff00000000ull) | w32)
+                                                : (((uint64_t)val[j] & 0xffffffffull) | (w32 << 32)));
+                }
+            __syncthreads();
+        }
+        shift += nbits;
+    }
+    uint32_t *kout = (uint32_t *)a.kout + b0;
+    ValT *vout = (ValT *)a.vout + b0;
+#pragma unroll
+    for (int j = 0; j < KPT; ++j)
+        if (e0 + (uint32_t)j * 64u < cnt) kout[e0 + (uint32_t)j * 64u] = key[j];
+#pragma unroll
+    for (int j = 0; j < KPT; ++j)
+        if (e0 + (uint32_t)j * 64u < cnt) vout[e0 + (uint32_t)j * 64u] = val[j];
+}
+
 struct rs_plan {
     uint32_t n = 0, seg_len = 0, nseg = 0, tps = 0, ntiles = 0, hbps = 0;
     int npass = 0, shift[RS_MAX_PASS], width[RS_MAX_PASS];
     size_t off_ticket = 0, off_status[RS_MAX_PASS], zero_bytes = 0, off_base = 0, off_data = 0, ctl_bytes = 0;
+    size_t off_tpre = 0, off_btot = 0, off_bbase = 0;  // the top-digit route's tables (topw > 0)
 };
 
 // digits: `bits` key bits in ceil(bits / 8) passes of (nearly) equal width
@@ -432,7 +680,23 @@ static void rs_split_bits(unsigned bits, int *npass, int *shift, int *width) {
     *npass = P;
 }
 
-static void rs_make_plan(rs_plan &pl, size_t n, size_t seg_len, unsigned bits, unsigned tile) {
+// The top digit's width for the top-digit route, 0: the sort keeps the LSD passes.  The narrowest digit (longest runs per (tile,
+// bucket) in the scatter) whose buckets -- seg_len pairs over the part of the 2^w buckets that ids below `krange` reach -- stay
+// under the finish's capacity with 6 sigma to spare.  krange = 0: the caller does not know the range (slk_probe_sort); ids may
+// fill as little as half of 2^bits, so that is tried first, then the full range (if the buckets turn out larger, `nofit` says so).
+static int rs_pick_topw(size_t seg_len, unsigned bits, size_t krange) {
+    const double full = ldexp(1.0, (int)bits);
+    double fill[2] = {0.5, 1.0};
+    if (krange) fill[0] = fill[1] = (double)krange < full ? (double)krange / full : 1.0;
+    for (int f = 0; f < 2; ++f)
+        for (int w = 1; w <= RS_RB; ++w) {
+            const double mean = (double)seg_len / (ldexp(1.0, w) * fill[f]);
+            if (mean + 6.0 * sqrt(mean) <= (double)RS_FIN_CAP) return w;
+        }
+    return 0;
+}
+
+static void rs_make_plan(rs_plan &pl, size_t n, size_t seg_len, unsigned bits, unsigned tile, int topw = 0) {
     pl.n = (uint32_t)n;
     pl.seg_len = (uint32_t)(seg_len && seg_len < n ? seg_len : n);
     pl.nseg = (uint32_t)((n + pl.seg_len - 1) / pl.seg_len);
@@ -451,6 +715,14 @@ static void rs_make_plan(rs_plan &pl, size_t n, size_t seg_len, unsigned bits, u
     o = (o + 255) & ~(size_t)255;
     pl.off_base = o;
     o += (size_t)pl.nseg * pl.npass * RS_RADIX * 4;
+    if (topw > 0) {
+        pl.off_tpre = o = (o + 255) & ~(size_t)255;
+        o += (size_t)pl.ntiles * ((size_t)1 << topw) * 4;
+        pl.off_btot = o = (o + 255) & ~(size_t)255;
+        o += (size_t)pl.nseg * RS_RADIX * 4;
+        pl.off_bbase = o;
+        o += (size_t)pl.nseg * RS_RADIX * 4;
+    }
     pl.off_data = (o + 255) & ~(size_t)255;
     pl.ctl_bytes = pl.off_data;
 }
@@ -481,9 +753,10 @@ static inline unsigned rs_tile_of(int cfg) { return cfg == 1 ? (unsigned)(RS_BIG
 // The sort.  Pass p reads what pass p - 1 wrote; the last pass writes (kout, vout).  Intermediate passes alternate between
 // (kout, vout) and a second buffer pair: (kalt, valt) when the caller has one (the training prep's double buffers, or an
 // input the caller allows to be overwritten), else space behind the control block in `scratch`.
+// krange: the keys' sorted bits are ids below this (0: not known) -- sizes the top-digit route's buckets.
 template <class KeyT, class ValT, int LOADER>
 static int rs_sort(slk_ctx *ctx, slk_buf &scratch, rs_args a, size_t n, size_t seg_len, unsigned bits, void *kalt, void *valt,
-                   hipStream_t s) {
+                   hipStream_t s, size_t krange = 0) {
     if (n == 0) return SLK_OK;
     if (n >= ((size_t)1 << 31)) return slk_fail(ctx, SLK_EINVAL, "sort of %zu pairs: at most 2^31 - 1", n);
     if (bits > 8 * sizeof(KeyT)) bits = 8 * sizeof(KeyT);
@@ -492,17 +765,24 @@ static int rs_sort(slk_ctx *ctx, slk_buf &scratch, rs_args a, size_t n, size_t s
     const bool single = LOADER == RS_LOAD_PLAIN && n <= 4096 && (seg_len == 0 || seg_len >= n);
     const int cfg = (!single && n >= (size_t)ctx->opt_sort_big_min) ? 1 : 0;
     const unsigned tile = rs_tile_of(cfg);
+    // the top-digit route: segmented sorts of u32 keys with the large sorts' tiles, more than one digit
+    int topw = 0;
+    if (sizeof(KeyT) == 4 && LOADER != RS_LOAD_FY_STEPS && cfg == 1 && seg_len > 0 && bits > (unsigned)RS_RB &&
+        (seg_len < n ? seg_len : n) >= ((size_t)ctx->opt_sort_big_min < (size_t)RS_FIN_MIN_SEG ? (size_t)ctx->opt_sort_big_min : (size_t)RS_FIN_MIN_SEG))
+        topw = rs_pick_topw(seg_len < n ? seg_len : n, bits, krange);
     rs_plan pl;
-    rs_make_plan(pl, n, single ? 0 : seg_len, bits, tile);
+    rs_make_plan(pl, n, single ? 0 : seg_len, bits, tile, topw);
     if (pl.seg_len >= (1u << 30)) return slk_fail(ctx, SLK_EINVAL, "sort segment of %u pairs: at most 2^30 - 1", pl.seg_len);
     // With the input as the second buffer pair (`clobber`) and an even number of passes the first pass would have to write over
-    // its own input: that one hop goes through the scratch instead.
+    // its own input: that one hop goes through the scratch instead.  (The top-digit scatter never writes over its input either.)
     const bool inplace0 = kalt && kalt == a.kin && (pl.npass & 1) == 0;
-    const bool need_tmp = pl.npass > 1 && (!kalt || inplace0);
+    const bool need_tmp = (pl.npass > 1 && (!kalt || inplace0)) || (topw && kalt && kalt == a.kin);
     const size_t koff = pl.off_data, voff = (koff + n * sizeof(KeyT) + 255) & ~(size_t)255;
     int rc = slk_ensure(ctx, scratch, need_tmp ? voff + n * sizeof(ValT) : pl.ctl_bytes);
     if (rc) return rc;
     char *base = (char *)scratch.p;
+    void *const kmid = (kalt && kalt != a.kin) ? kalt : (void *)(base + koff);  // top-digit route: scatter -> (kmid, vmid) -> finish
+    void *const vmid = (kalt && kalt != a.kin) ? valt : (void *)(base + voff);
     void *k0dst = nullptr, *v0dst = nullptr;  // destination of pass 0 when it is neither the final nor the alternate pair
     if (need_tmp && !kalt) {
         kalt = base + koff;
@@ -529,8 +809,40 @@ static int rs_sort(slk_ctx *ctx, slk_buf &scratch, rs_args a, size_t n, size_t s
     a.nseg = pl.nseg;
     a.xcd = pl.nseg >= 2 ? 1 : 0;
     void *kfinal = a.kout, *vfinal = a.vout;
+    if (!single) SLK_HIP(ctx, hipMemsetAsync(base, 0, pl.zero_bytes, s));
+    if constexpr (sizeof(KeyT) == 4 && LOADER != RS_LOAD_FY_STEPS) {
+        if (topw) {
+            a.topw = topw;
+            a.topshift = (int)bits - topw;
+            a.tpre = (uint32_t *)(base + pl.off_tpre);
+            a.btot = (uint32_t *)(base + pl.off_btot);
+            a.bbase = (uint32_t *)(base + pl.off_bbase);
+            a.nofit = a.ticket + 120;  // (inside the zeroed ticket block, behind the tickets)
+            a.fallbacks = &ctx->d_rng->sort_fallbacks;
+            const unsigned ngr = (1u << topw) < 32u ? 1u : (1u << topw) / 32u;
+            hipLaunchKernelGGL((k_rs_tile_hist<KeyT, LOADER, RS_BIG_THREADS, RS_BIG_KPT>), dim3(pl.ntiles), dim3(RS_BIG_THREADS), 0, s, a);
+            SLK_LAUNCH_CHECK(ctx, "k_rs_tile_hist");
+            hipLaunchKernelGGL(k_rs_tile_scan, dim3(pl.nseg * ngr), dim3(256), 0, s, a);
+            SLK_LAUNCH_CHECK(ctx, "k_rs_tile_scan");
+            hipLaunchKernelGGL(k_rs_bucket_base, dim3(pl.nseg), dim3(256), 0, s, a);
+            SLK_LAUNCH_CHECK(ctx, "k_rs_bucket_base");
+            rs_args t = a;
+            t.kout = kmid;
+            t.vout = vmid;
+            hipLaunchKernelGGL((k_rs_scatter<KeyT, ValT, RS_BIG_THREADS, RS_BIG_KPT, LOADER, false, true>), dim3(pl.ntiles), dim3(RS_BIG_THREADS),
+                               0, s, t);
+            SLK_LAUNCH_CHECK(ctx, "k_rs_scatter (top digit)");
+            t.kin = kmid;
+            t.vin = vmid;
+            t.kout = kfinal;
+            t.vout = vfinal;
+            hipLaunchKernelGGL((k_rs_finish<ValT>), dim3(pl.nseg << topw), dim3(RS_FIN_THREADS), 0, s, t);
+            SLK_LAUNCH_CHECK(ctx, "k_rs_finish");
+            a.gate = 1;  // the LSD kernels below: only when a bucket did not fit
+            ++ctx->stat_sort_finish_sorts;
+        }
+    }
     if (!single) {
-        SLK_HIP(ctx, hipMemsetAsync(base, 0, pl.zero_bytes, s));
         a.pass = 0;
         hipLaunchKernelGGL((k_rs_hist<KeyT, LOADER>), dim3(pl.nseg * pl.hbps), dim3(256), 0, s, a);
         SLK_LAUNCH_CHECK(ctx, "k_rs_hist");
@@ -644,47 +956,49 @@ int slk_sort_pairs_any(slk_ctx *ctx, int kind, const void *kin, void *kout, cons
 static bool rs_segmented(size_t n, size_t seg_len) { return seg_len < n && seg_len >= 32768; }
 
 template <class KeyT, class ValT, int LOADER>
-static int rs_sort_fused(slk_ctx *ctx, rs_args a, size_t n, size_t seg_len, unsigned idbits, unsigned mbbits, void *const key[2],
-                         void *const val[2], hipStream_t s) {
+static int rs_sort_fused(slk_ctx *ctx, rs_args a, size_t n, size_t seg_len, unsigned idbits, unsigned mbbits, size_t nids,
+                         void *const key[2], void *const val[2], hipStream_t s) {
     a.idbits = idbits;
     a.kout = key[1];
     a.vout = val[1];
     const bool seg = rs_segmented(n, seg_len), one = seg_len >= n;  // one: a single minibatch, its number (0) needs no bits
     a.kseg = seg ? 0u : (uint32_t)seg_len;
     return rs_sort<KeyT, ValT, LOADER>(ctx, ctx->sort_tmp, a, n, seg ? seg_len : 0, (seg || one) ? idbits : idbits + mbbits, key[0],
-                                       val[0], s);
+                                       val[0], s, nids);
 }
 
 // interactions of a chunk -> (key = (minibatch, user), payload = (negative << 32 | positive)) sorted by key, stable; the result
 // in (key[1], val[1]), (key[0], val[0]) is scratch
 int slk_sort_user_fat(slk_ctx *ctx, const int64_t *users, const int64_t *items, const uint32_t *neg32, size_t nc, size_t bsz,
-                      unsigned ubits, unsigned mbbits, uint32_t *const key[2], uint64_t *const val[2], hipStream_t s) {
+                      unsigned ubits, unsigned mbbits, size_t num_users, uint32_t *const key[2], uint64_t *const val[2], hipStream_t s) {
     rs_args a;
     memset(&a, 0, sizeof(a));
     a.users = users;
     a.items = items;
     a.neg32 = neg32;
-    return rs_sort_fused<uint32_t, uint64_t, RS_LOAD_USER_FAT>(ctx, a, nc, bsz, ubits, mbbits, (void *const *)key, (void *const *)val, s);
+    return rs_sort_fused<uint32_t, uint64_t, RS_LOAD_USER_FAT>(ctx, a, nc, bsz, ubits, mbbits, num_users, (void *const *)key, (void *const *)val, s);
 }
 
 // same keys, payload = the interaction's index in the chunk (the routes whose dL/dscore exists before the user pass)
-int slk_sort_user_idx(slk_ctx *ctx, const int64_t *users, size_t nc, size_t bsz, unsigned ubits, unsigned mbbits,
+int slk_sort_user_idx(slk_ctx *ctx, const int64_t *users, size_t nc, size_t bsz, unsigned ubits, unsigned mbbits, size_t num_users,
                       uint32_t *const key[2], uint32_t *const val[2], hipStream_t s) {
     rs_args a;
     memset(&a, 0, sizeof(a));
     a.users = users;
-    return rs_sort_fused<uint32_t, uint32_t, RS_LOAD_USER_IDX>(ctx, a, nc, bsz, ubits, mbbits, (void *const *)key, (void *const *)val, s);
+    return rs_sort_fused<uint32_t, uint32_t, RS_LOAD_USER_IDX>(ctx, a, nc, bsz, ubits, mbbits, num_users, (void *const *)key, (void *const *)val, s);
 }
 
 // occurrences r of the packed item list uit[nocc] (NP per user-sorted position) -> (key = (minibatch, item), payload = r)
 int slk_sort_item_occ(slk_ctx *ctx, const uint32_t *uit, size_t nocc, size_t bsz, int NP, unsigned ibits, unsigned mbbits,
-                      uint32_t *const key[2], uint32_t *const val[2], hipStream_t s) {
+                      size_t num_items, uint32_t *const key[2], uint32_t *const val[2], hipStream_t s) {
     rs_args a;
     memset(&a, 0, sizeof(a));
     a.uit = uit;
-    return rs_sort_fused<uint32_t, uint32_t, RS_LOAD_ITEM_OCC>(ctx, a, nocc, bsz * (size_t)NP, ibits, mbbits, (void *const *)key,
+    return rs_sort_fused<uint32_t, uint32_t, RS_LOAD_ITEM_OCC>(ctx, a, nocc, bsz * (size_t)NP, ibits, mbbits, num_items, (void *const *)key,
                                                                (void *const *)val, s);
 }
+
+int64_t slk_sort_finish_cap(void) { return (int64_t)RS_FIN_CAP; }
 
 // Sizes ctx->sort_tmp's control block (histograms, tickets, look-back words) for sorts of up to n pairs, so that a training
 // call allocates nothing; the second buffer pair of a sort without one is added on demand.
@@ -695,5 +1009,8 @@ int slk_sort_reserve(slk_ctx *ctx, size_t n) {
     size_t need = pl.ctl_bytes;
     // a segmented plan of the same size has one partial tile per segment more: bounded by 2 x the tiles
     need += (size_t)pl.ntiles * RS_RADIX * 4 * 4;
+    // the top-digit route's tables: 2^8 counts per tile of RS_BIG_THREADS x RS_BIG_KPT pairs (one partial tile per segment more;
+    // segmented chunks have segments of >= 32768 pairs), and two words per (segment, bucket)
+    need += ((n / rs_tile_of(1)) + n / 32768 + 2) * RS_RADIX * 4 + (n / 32768 + 2) * RS_RADIX * 8 + 1024;
     return slk_ensure(ctx, ctx->sort_tmp, need);
 }
