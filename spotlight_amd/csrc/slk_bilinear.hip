@@ -661,8 +661,19 @@ struct slk_sweep_all_args {
     size_t numel[4];
     unsigned first[5];
     int adam;
-    float wd, w1, beta2, omb2, step_size, bc2_sqrt, eps, clr;
+    slk_opt_coef coef;
+    slk_opt_hyper hyper;
 };
+
+// One element: consume (and re-zero) its gradient, then the optimizer's rule in place on memory -- the state's stores are
+// issued where the rule assigns them, ahead of the parameter's division chain.
+template <int KIND>
+__device__ __forceinline__ void slk_dense_sweep_elem(const slk_sweep_all_args &a, float *p, float *s1, float *s2, float *g, size_t e) {
+    const float gv = g[e];
+    g[e] = 0.0f;
+    float none = 0.0f;
+    slk_opt_step<KIND>(a.hyper, a.coef, p[e], s1[e], slk_opt_has_s2(KIND) ? s2[e] : none, gv);
+}
 
 __global__ __launch_bounds__(256) void k_dense_sweep_all(slk_sweep_all_args a) {
     int t = 0;
@@ -671,26 +682,9 @@ __global__ __launch_bounds__(256) void k_dense_sweep_all(slk_sweep_all_args a) {
     float *p = a.p[t], *s1 = a.s1[t], *s2 = a.s2[t], *g = a.g[t];
     const size_t numel = a.numel[t];
     if (a.adam) {
-        // torch/optim/adam.py:414-546 (single-tensor): g += wd*p; m.lerp_(g, 1-b1);
-        // v = b2*v + (1-b2) g^2; p += -(lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-        for (size_t e = local * 256 + threadIdx.x; e < numel; e += nblk * 256) {
-            const float gv = g[e] + a.wd * p[e];
-            g[e] = 0.0f;
-            const float m = s1[e] + a.w1 * (gv - s1[e]);
-            const float v = s2[e] * a.beta2 + a.omb2 * (gv * gv);
-            s1[e] = m;
-            s2[e] = v;
-            p[e] += -a.step_size * (m / (sqrtf(v) / a.bc2_sqrt + a.eps));
-        }
+        for (size_t e = local * 256 + threadIdx.x; e < numel; e += nblk * 256) slk_dense_sweep_elem<SLK_OPT_ADAM_DENSE>(a, p, s1, s2, g, e);
     } else {
-        // torch/optim/adagrad.py:350-385 dense branch with weight_decay
-        for (size_t e = local * 256 + threadIdx.x; e < numel; e += nblk * 256) {
-            const float gv = g[e] + a.wd * p[e];
-            g[e] = 0.0f;
-            const float s = s1[e] + gv * gv;
-            s1[e] = s;
-            p[e] += -a.clr * (gv / (sqrtf(s) + a.eps));
-        }
+        for (size_t e = local * 256 + threadIdx.x; e < numel; e += nblk * 256) slk_dense_sweep_elem<SLK_OPT_ADAGRAD_DENSE>(a, p, s1, s2, g, e);
     }
 }
 
@@ -930,7 +924,7 @@ int slk_check_optim(slk_ctx *ctx, const slk_optim *optim, unsigned table_mask) {
         if (optim->weight_decay != 0.0) return slk_fail(ctx, SLK_EINVAL, "SGD: weight_decay must be 0 (a full-table sweep per step is not built)");
         return SLK_OK;
     }
-    const bool need_s2 = optim->kind == SLK_OPT_SPARSE_ADAM || optim->kind == SLK_OPT_ADAM_DENSE;
+    const bool need_s2 = slk_opt_has_s2(optim->kind);
     for (int i = 0; i < 4; ++i) {
         if (!((table_mask >> i) & 1u)) continue;
         if (!optim->d_state1[i]) return slk_fail(ctx, SLK_EINVAL, "optim->d_state1[%d] is NULL", i);
@@ -958,23 +952,12 @@ int slk_ensure_dgrad(slk_ctx *ctx, const size_t elems[4], unsigned table_mask, h
 // the tables in `table_mask`, consuming (and re-zeroing) the dense gradient buffers.
 int slk_dense_sweeps(slk_ctx *ctx, float *const params[4], const slk_optim *optim, unsigned table_mask,
                      hipStream_t s) {
-    const double step = (double)(optim->step + 1);
     slk_prof_begin(ctx, SLK_K_DENSE_SWEEP, s);
     slk_sweep_all_args w;
     memset(&w, 0, sizeof(w));
-    w.wd = (float)optim->weight_decay;
-    w.eps = (float)optim->eps;
     w.adam = optim->kind == SLK_OPT_ADAM_DENSE;
-    if (w.adam) {
-        const double bc1 = 1.0 - pow(optim->beta1, step), bc2 = 1.0 - pow(optim->beta2, step);
-        w.w1 = (float)(1.0 - optim->beta1);
-        w.beta2 = (float)optim->beta2;
-        w.omb2 = (float)(1.0 - optim->beta2);
-        w.step_size = (float)(optim->lr / bc1);
-        w.bc2_sqrt = (float)sqrt(bc2);
-    } else {
-        w.clr = (float)(optim->lr / (1.0 + (step - 1.0) * optim->lr_decay));
-    }
+    w.coef = slk_opt_coef_at(optim, optim->step + 1);
+    w.hyper = slk_opt_hyper_of(optim);
     unsigned blocks = 0;
     for (int t = 0; t < 4; ++t) {
         w.first[t] = blocks;
@@ -1187,7 +1170,7 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
     p.nn = p.adaptive ? c.n_neg : (p.expl ? 0 : 1);
     if (!p.expl && (p.nn < 1 || p.nn > 1024)) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", p.nn);
     p.NP = p.nn + 1;
-    p.dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    p.dense = slk_opt_is_dense(optim->kind);
     if (n == 0) return SLK_OK;
     if (!reserve && (!c.users || !c.items || (!c.mb_loss && !prefetch)))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: NULL id/loss pointer");
@@ -1633,7 +1616,7 @@ static void chunk_pass_args(slk_ctx *ctx, const train_plan &p, const train_call 
     // user biases the caller vouches are all zero, a loss whose user-bias gradient is exactly zero, an update for which a
     // zero gradient is an exact no-op: nothing of the table is read or written by the pair-mode user pass
     a.ubz = (tables->flags & SLK_TABLES_USER_BIAS_ZERO) && (c.loss == SLK_LOSS_BPR || c.loss == SLK_LOSS_HINGE) && !p.bloom &&
-            (optim->kind == SLK_OPT_ADAGRAD || optim->kind == SLK_OPT_SGD) && ctx->opt_user_bias_zero_hint;
+            slk_opt_zero_is_noop(optim->kind) && ctx->opt_user_bias_zero_hint;
     a.nt = ctx->opt_nt;
     if (p.fused) a.ratings = c.ratings + chunk_begin(p, ck);  // the user pass forms score, loss and dL/dscore itself (one pair per interaction)
 }

@@ -221,7 +221,7 @@ struct slk_ctx {
     int64_t opt_epoch_dense_elems = (int64_t)1 << 18;  // dense optimizers: largest model (parameters) the persistent route takes:
                                    // every row group sweeps rows / row-groups rows per phase, so only models of the reference's own
                                    // scale (MovieLens-100K at dim 32: 87 K parameters)
-    void *h_coef[2] = {nullptr, nullptr};  // pinned host staging of the per-minibatch optimizer coefficients (slk_step_coef),
+    void *h_coef[2] = {nullptr, nullptr};  // pinned host staging of the per-minibatch optimizer coefficients (slk_opt_coef),
     size_t h_coef_cap[2] = {0, 0};         //   double-buffered: ev_coef[b] is recorded behind the copy issued from buffer b
     hipEvent_t ev_coef[2] = {nullptr, nullptr};
     int coef_flip = 0;

@@ -46,19 +46,8 @@
 // spread over 4x as many CUs the same work measured 18.8 -> see profiles/ us per minibatch at C1 shape, minibatch 1024.
 #define SLK_EPOCH_TB 64
 
-enum { SLK_EUPD_ADAGRAD = 0, SLK_EUPD_SPARSE_ADAM = 1, SLK_EUPD_ADAM_DENSE = 2, SLK_EUPD_ADAGRAD_DENSE = 3, SLK_EUPD_SGD = 4 };
-// a zero summed gradient leaves the row exactly as it is: row-sparse Adagrad and SGD
-#define SLK_EUPD_ZERO_IS_NOOP(UPD) ((UPD) == SLK_EUPD_ADAGRAD || (UPD) == SLK_EUPD_SGD)
-
 #define SLK_EPOCH_ABORT 0xffffffffu
 #define SLK_EPOCH_MAX_SPINS (1u << 24)  // x (s_sleep + one fabric round trip): seconds
-
-// per-minibatch optimizer coefficients, formed on the host in double exactly as torch does (bias corrections and
-// lr decay depend on the step count)
-struct slk_step_coef {
-    float c0;  // Adagrad (sparse / dense): clr.  SparseAdam: lr * sqrt(bc2) / bc1.  Adam dense: lr / bc1
-    float c1;  // Adam dense: sqrt(bc2)
-};
 
 struct slk_epoch_args {
     float *P[4], *S1[4], *S2[4];
@@ -78,12 +67,12 @@ struct slk_epoch_args {
     float *gsn;                    // [2 * (position - b0) + pair] dL/dscore (explicit: [position - b0])
     double *partial;               // [n_mb][gridDim.x] per-workgroup loss sums
     float *mb_loss;                // [n_mb] loss.item() of each minibatch
-    const slk_step_coef *coef;     // [n_mb]
+    const slk_opt_coef *coef;      // [n_mb] per-minibatch optimizer coefficients (bias corrections and lr decay depend on the step count)
     uint32_t *touch_u, *touch_i;   // dense optimizers: touch[row] = (last minibatch that looks the row up) + 1; zeroed before the launch
     unsigned *bar;                 // barrier counter, zeroed before the launch
     int *status;                   // barrier time-out: the number (>= 1) of the barrier that was abandoned, 2 per minibatch (adaptive: 3)
     int loss_kind;
-    float eps, omb1, omb2, beta2, wd;
+    slk_opt_hyper hyper;
     int bar_kind;                  // 0: one arrival counter, 1: 8 sub-counters + a top counter
     int debug;                     // measurement only (option "epoch_debug"): 1 skip the phases' work, 2 do not wait at barriers, 4 no drain,
                                    // 8 / 16 / 32 skip the user (sequence) / item / score phase alone
@@ -141,67 +130,15 @@ __device__ __forceinline__ bool slk_epoch_barrier(const slk_epoch_args &e, unsig
     return *s_flag != 0;  // the caller alternates between two flag words, so no third barrier is needed
 }
 
-// ---- row updates: the arithmetic of slk_apply_vec / k_dense_sweep_all, element for element, on coherent accesses -------
+// ---- row updates: the optimizer's rule (slk_opt_step; UPD is an SLK_OPT_* kind) and its stores, on coherent accesses -------
 template <int VEC, int UPD>
-__device__ __forceinline__ void slk_epoch_update(const slk_epoch_args &e, const slk_step_coef &c, int t, size_t off,
+__device__ __forceinline__ void slk_epoch_update(const slk_epoch_args &e, const slk_opt_coef &c, int t, size_t off,
                                                  slk_vec<VEC> p, slk_vec<VEC> s1, slk_vec<VEC> s2, const slk_vec<VEC> &g) {
-    if (UPD == SLK_EUPD_ADAGRAD) {  // torch/optim/adagrad.py:360-385
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            s1.v[i] += g.v[i] * g.v[i];
-            p.v[i] += -c.c0 * (g.v[i] / (sqrtf(s1.v[i]) + e.eps));
-        }
-        slk_vstore_coh<VEC>(e.S1[t] + off, s1);
-    } else if (UPD == SLK_EUPD_SPARSE_ADAM) {  // torch/optim/_functional.py:61-84
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const float mu = (g.v[i] - s1.v[i]) * e.omb1;
-            const float vu = (g.v[i] * g.v[i] - s2.v[i]) * e.omb2;
-            s1.v[i] = mu + s1.v[i];
-            s2.v[i] = vu + s2.v[i];
-            p.v[i] += -c.c0 * (s1.v[i] / (sqrtf(s2.v[i]) + e.eps));
-        }
-        slk_vstore_coh<VEC>(e.S1[t] + off, s1);
-        slk_vstore_coh<VEC>(e.S2[t] + off, s2);
-    } else if (UPD == SLK_EUPD_SGD) {  // torch/optim/sgd.py, momentum 0, weight_decay 0: param.add_(grad, alpha=-lr)
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) p.v[i] += -c.c0 * g.v[i];
-    } else if (UPD == SLK_EUPD_ADAM_DENSE) {  // torch/optim/adam.py:414-546 (k_dense_sweep_all)
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const float gv = g.v[i] + e.wd * p.v[i];
-            const float m = s1.v[i] + e.omb1 * (gv - s1.v[i]);
-            const float v = s2.v[i] * e.beta2 + e.omb2 * (gv * gv);
-            s1.v[i] = m;
-            s2.v[i] = v;
-            p.v[i] += -c.c0 * (m / (sqrtf(v) / c.c1 + e.eps));
-        }
-        slk_vstore_coh<VEC>(e.S1[t] + off, s1);
-        slk_vstore_coh<VEC>(e.S2[t] + off, s2);
-    } else {  // torch/optim/adagrad.py:350-385, dense branch with weight decay
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const float gv = g.v[i] + e.wd * p.v[i];
-            const float s = s1.v[i] + gv * gv;
-            s1.v[i] = s;
-            p.v[i] += -c.c0 * (gv / (sqrtf(s) + e.eps));
-        }
-        slk_vstore_coh<VEC>(e.S1[t] + off, s1);
-    }
+    for (int i = 0; i < VEC; ++i) slk_opt_step<UPD>(e.hyper, c, p.v[i], s1.v[i], s2.v[i], g.v[i]);
+    if (slk_opt_has_s1(UPD)) slk_vstore_coh<VEC>(e.S1[t] + off, s1);
+    if (slk_opt_has_s2(UPD)) slk_vstore_coh<VEC>(e.S2[t] + off, s2);
     slk_vstore_coh<VEC>(e.P[t] + off, p);
-}
-
-template <int UPD>
-__device__ __forceinline__ constexpr bool slk_epoch_has_s2() {
-    return UPD == SLK_EUPD_SPARSE_ADAM || UPD == SLK_EUPD_ADAM_DENSE;
-}
-template <int UPD>
-__device__ __forceinline__ constexpr bool slk_epoch_has_s1() {
-    return UPD != SLK_EUPD_SGD;
-}
-template <int UPD>
-__device__ __forceinline__ constexpr bool slk_epoch_dense() {
-    return UPD == SLK_EUPD_ADAM_DENSE || UPD == SLK_EUPD_ADAGRAD_DENSE;
 }
 
 // Dense optimizers (the reference's default Adam + l2, Adagrad + weight decay): EVERY row is updated every step, the rows a
@@ -212,7 +149,7 @@ __device__ __forceinline__ constexpr bool slk_epoch_dense() {
 // gradient.  Balanced (rows / row groups iterations per phase), no gradient buffer, no third phase; the arithmetic is
 // k_dense_sweep_all's element for element.
 template <int VEC, int UPD>
-__device__ __forceinline__ void slk_epoch_sweep_untouched(const slk_epoch_args &e, const slk_step_coef &c, int te, int tb,
+__device__ __forceinline__ void slk_epoch_sweep_untouched(const slk_epoch_args &e, const slk_opt_coef &c, int te, int tb,
                                                           const uint32_t *touch, uint32_t want, uint32_t n_rows, uint32_t gslot,
                                                           uint32_t gstride, int D, int d0, bool on, int lane) {
     for (uint32_t r = gslot; r < n_rows; r += gstride) {
@@ -224,12 +161,12 @@ __device__ __forceinline__ void slk_epoch_sweep_untouched(const slk_epoch_args &
             const size_t off = (size_t)r * D + d0;
             p = slk_vload_coh<VEC>(e.P[te] + off);
             s1 = slk_vload_coh<VEC>(e.S1[te] + off);
-            if (slk_epoch_has_s2<UPD>()) s2 = slk_vload_coh<VEC>(e.S2[te] + off);
+            if (slk_opt_has_s2(UPD)) s2 = slk_vload_coh<VEC>(e.S2[te] + off);
         }
         if (lane == 0) {
             bp = slk_vload_coh<1>(e.P[tb] + r);
             bs1 = slk_vload_coh<1>(e.S1[tb] + r);
-            if (slk_epoch_has_s2<UPD>()) bs2 = slk_vload_coh<1>(e.S2[tb] + r);
+            if (slk_opt_has_s2(UPD)) bs2 = slk_vload_coh<1>(e.S2[tb] + r);
         }
         if (stamp == want) continue;  // touched: its owner applies the summed gradient
         if (on) slk_epoch_update<VEC, UPD>(e, c, te, (size_t)r * D + d0, p, s1, s2, slk_vzero<VEC>());
@@ -250,11 +187,11 @@ enum { SLK_EI_PAIR = 0, SLK_EI_EXPL = 1, SLK_EI_ADP = 2 };
 #endif
 
 template <int VEC, int G, int UPD, int IMODE>
-__device__ __forceinline__ void slk_epoch_item_phase(const slk_epoch_args &e, const slk_step_coef &c, uint32_t b0, uint32_t ib0,
+__device__ __forceinline__ void slk_epoch_item_phase(const slk_epoch_args &e, const slk_opt_coef &c, uint32_t b0, uint32_t ib0,
                                                      uint32_t ib1, uint32_t NP, uint32_t gslot, uint32_t gstride, int D, int d0,
                                                      bool on, int lane, uint32_t nx_key, uint32_t nx_prev, uint32_t nx_a) {
-    constexpr bool HAS_S2 = slk_epoch_has_s2<UPD>();
-    constexpr bool HAS_S1 = slk_epoch_has_s1<UPD>();
+    constexpr bool HAS_S2 = slk_opt_has_s2(UPD);
+    constexpr bool HAS_S1 = slk_opt_has_s1(UPD);
     constexpr int NB = SLK_EPOCH_ITEM_BATCH;
     const slk_vec<VEC> zero = slk_vzero<VEC>();
     const slk_vec<1> zero1 = slk_vzero<1>();
@@ -392,9 +329,9 @@ __device__ __forceinline__ void slk_epoch_item_phase(const slk_epoch_args &e, co
 
             // Adagrad: a run without any gradient is an exact no-op; SparseAdam decays the moments of every looked-up
             // row; the dense optimizers update every row anyway
-            if (!(SLK_EUPD_ZERO_IS_NOOP(UPD) && !any)) {
+            if (!(slk_opt_zero_is_noop(UPD) && !any)) {
                 if (on) slk_epoch_update<VEC, UPD>(e, c, 1, voff, v[i], sv1[i], sv2[i], gv);
-                if (lane == 0 && !(SLK_EUPD_ZERO_IS_NOOP(UPD) && gb == 0.0f)) {
+                if (lane == 0 && !(slk_opt_zero_is_noop(UPD) && gb == 0.0f)) {
                     slk_vec<1> bp, bg;
                     bp.v[0] = bi[i];
                     bg.v[0] = gb;
@@ -416,9 +353,9 @@ __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args 
     if (threadIdx.x < 4) s_wave_sums[threadIdx.x] = 0.0;
     constexpr int TB = SLK_EPOCH_TB, NW = TB / 64;
     constexpr int GPB = TB / G;
-    constexpr bool DENSE = slk_epoch_dense<UPD>();
-    constexpr bool HAS_S2 = slk_epoch_has_s2<UPD>();
-    constexpr bool HAS_S1 = slk_epoch_has_s1<UPD>();
+    constexpr bool DENSE = slk_opt_is_dense(UPD);
+    constexpr bool HAS_S2 = slk_opt_has_s2(UPD);
+    constexpr bool HAS_S1 = slk_opt_has_s1(UPD);
     const int lane = threadIdx.x % G, grp = threadIdx.x / G;
     const int D = e.D, d0 = lane * VEC;
     const bool on = d0 < D;
@@ -464,7 +401,7 @@ __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args 
     for (uint32_t mb = 0; mb < e.n_mb; ++mb) {
         const uint32_t b0 = mb * e.bsz, b1 = (e.nc - b0 < e.bsz) ? e.nc : b0 + e.bsz;
         const float inv_b = 1.0f / (float)(b1 - b0);
-        const slk_step_coef c = e.coef[mb];
+        const slk_opt_coef c = e.coef[mb];
 
         // ------------------------------------------------ SCORE PHASE (adaptive hinge): k_score_pass's arithmetic
         if (ADP) {
@@ -686,7 +623,7 @@ __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args 
                 gbu = gbl;
             }
             if (on) slk_epoch_update<VEC, UPD>(e, c, 0, uoff, u, su1, su2, gu);
-            if (lane == 0 && !(SLK_EUPD_ZERO_IS_NOOP(UPD) && gbu == 0.0f)) {  // zero gradient: an exact no-op for Adagrad
+            if (lane == 0 && !(slk_opt_zero_is_noop(UPD) && gbu == 0.0f)) {  // zero gradient: an exact no-op for Adagrad
                 slk_vec<1> bp, bg;
                 bp.v[0] = bu;
                 bg.v[0] = gbu;
@@ -770,11 +707,11 @@ typedef void (*slk_epoch_fn)(slk_epoch_args);
 template <int VEC, int G, int MODE>
 static slk_epoch_fn epoch_fn_of(int upd) {
     switch (upd) {
-        case SLK_EUPD_ADAGRAD: return k_bilinear_epoch<VEC, G, SLK_EUPD_ADAGRAD, MODE>;
-        case SLK_EUPD_SPARSE_ADAM: return k_bilinear_epoch<VEC, G, SLK_EUPD_SPARSE_ADAM, MODE>;
-        case SLK_EUPD_ADAM_DENSE: return k_bilinear_epoch<VEC, G, SLK_EUPD_ADAM_DENSE, MODE>;
-        case SLK_EUPD_SGD: return k_bilinear_epoch<VEC, G, SLK_EUPD_SGD, MODE>;
-        default: return k_bilinear_epoch<VEC, G, SLK_EUPD_ADAGRAD_DENSE, MODE>;
+        case SLK_OPT_ADAGRAD: return k_bilinear_epoch<VEC, G, SLK_OPT_ADAGRAD, MODE>;
+        case SLK_OPT_SPARSE_ADAM: return k_bilinear_epoch<VEC, G, SLK_OPT_SPARSE_ADAM, MODE>;
+        case SLK_OPT_ADAM_DENSE: return k_bilinear_epoch<VEC, G, SLK_OPT_ADAM_DENSE, MODE>;
+        case SLK_OPT_SGD: return k_bilinear_epoch<VEC, G, SLK_OPT_SGD, MODE>;
+        default: return k_bilinear_epoch<VEC, G, SLK_OPT_ADAGRAD_DENSE, MODE>;
     }
 }
 template <int VEC, int G>
@@ -797,21 +734,10 @@ bool slk_epoch_eligible(const slk_ctx *ctx, const slk_tables *tables, const slk_
         (!ctx->opt_epoch_adaptive || bsz > ctx->opt_epoch_adaptive_max_batch || bsz >= ctx->opt_adaptive_late_min_batch))
         return false;
     if (bsz > ctx->opt_epoch_max_batch) return false;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
     // the dense optimizers rewrite every row every minibatch: in one launch of at most one workgroup per CU that
     // is only sensible for tables that are small next to the chip's caches
-    if (dense && (tables->num_users + tables->num_items) * (int64_t)(tables->dim + 1) > ctx->opt_epoch_dense_elems) return false;
+    if (slk_opt_is_dense(optim->kind) && (tables->num_users + tables->num_items) * (int64_t)(tables->dim + 1) > ctx->opt_epoch_dense_elems) return false;
     return true;
-}
-
-static int epoch_upd_of(const slk_optim *optim) {
-    switch (optim->kind) {
-        case SLK_OPT_ADAGRAD: return SLK_EUPD_ADAGRAD;
-        case SLK_OPT_SPARSE_ADAM: return SLK_EUPD_SPARSE_ADAM;
-        case SLK_OPT_ADAM_DENSE: return SLK_EUPD_ADAM_DENSE;
-        case SLK_OPT_SGD: return SLK_EUPD_SGD;
-        default: return SLK_EUPD_ADAGRAD_DENSE;
-    }
 }
 
 // Workgroups of the persistent launch: one position per row group in the (2x longer) item phase when the chip allows, at most
@@ -822,7 +748,7 @@ static unsigned epoch_grid(slk_ctx *ctx, const slk_tables *tables, const slk_opt
                            slk_epoch_fn fn, size_t lds) {
     const unsigned gpb = (unsigned)SLK_EPOCH_TB / (unsigned)g;
     unsigned grid = (unsigned)((np * bsz + gpb - 1) / gpb);
-    if (optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE) {
+    if (slk_opt_is_dense(optim->kind)) {
         // the dense optimizers also sweep every row of the larger table once per phase: one row per row group if the chip allows
         const int64_t rows = tables->num_users > tables->num_items ? tables->num_users : tables->num_items;
         const unsigned by_rows = (unsigned)((rows + gpb - 1) / gpb);
@@ -861,12 +787,12 @@ static const size_t kEpochLds = 4 * sizeof(double) + 16;
 int slk_epoch_reserve(slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, uint32_t n_mb, int64_t bsz, int loss, int NP) {
     int vec, g, rc;
     if (!slk_pick_layout(tables->dim, &vec, &g)) return slk_fail(ctx, SLK_EINVAL, "embedding dim %d unsupported", tables->dim);
-    const unsigned grid = epoch_grid(ctx, tables, optim, bsz, (unsigned)NP, g, epoch_pick_fn(vec, g, epoch_upd_of(optim), epoch_mode_of(loss)),
+    const unsigned grid = epoch_grid(ctx, tables, optim, bsz, (unsigned)NP, g, epoch_pick_fn(vec, g, optim->kind, epoch_mode_of(loss)),
                                      kEpochLds);
-    if ((rc = slk_ensure(ctx, ctx->extra[EP_COEF], (size_t)n_mb * sizeof(slk_step_coef)))) return rc;
+    if ((rc = slk_ensure(ctx, ctx->extra[EP_COEF], (size_t)n_mb * sizeof(slk_opt_coef)))) return rc;
     if ((rc = slk_ensure(ctx, ctx->extra[EP_BAR], 2048))) return rc;
     if ((rc = slk_ensure(ctx, ctx->extra[EP_PARTIAL], (size_t)n_mb * (grid ? grid : 1) * 8))) return rc;
-    if (optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE) {
+    if (slk_opt_is_dense(optim->kind)) {
         const size_t rows = (size_t)tables->num_users + (size_t)tables->num_items;
         if ((rc = slk_ensure(ctx, ctx->extra[EP_TOUCH], rows * 4))) return rc;
     }
@@ -879,7 +805,7 @@ int slk_epoch_reserve(slk_ctx *ctx, const slk_tables *tables, const slk_optim *o
         ctx->h_coef[b] = nullptr;
         ctx->h_coef_cap[b] = 0;
         const size_t cap = n_mb < 1024 ? 1024 : n_mb;
-        SLK_HIP(ctx, hipHostMalloc(&ctx->h_coef[b], cap * sizeof(slk_step_coef), hipHostMallocDefault));
+        SLK_HIP(ctx, hipHostMalloc(&ctx->h_coef[b], cap * sizeof(slk_opt_coef), hipHostMallocDefault));
         ctx->h_coef_cap[b] = cap;
         if (!ctx->ev_coef[b]) SLK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_coef[b], hipEventDisableTiming));
     }
@@ -896,8 +822,7 @@ int slk_epoch_run_chunk(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim
     int vec, g, rc;
     if (!slk_pick_layout(tables->dim, &vec, &g)) return slk_fail(ctx, SLK_EINVAL, "embedding dim %d unsupported", tables->dim);
     const uint32_t n_mb = (uint32_t)((nc + bsz - 1) / bsz);
-    const int upd = epoch_upd_of(optim);
-    slk_epoch_fn fn = epoch_pick_fn(vec, g, upd, mode);
+    slk_epoch_fn fn = epoch_pick_fn(vec, g, optim->kind, mode);
     const size_t lds = kEpochLds;
     const unsigned grid = epoch_grid(ctx, tables, optim, bsz, (unsigned)NP, g, fn, lds);
     if (grid == 0) {  // the occupancy query says no workgroup of this kernel fits a CU: nothing ran, take the launch path
@@ -907,33 +832,16 @@ int slk_epoch_run_chunk(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim
     }
     if ((rc = slk_epoch_reserve(ctx, tables, optim, n_mb, bsz, loss, NP))) return rc;
 
-    // per-step coefficients, in double like torch (slk_set_opt_coeffs / slk_dense_sweeps)
+    // per-minibatch coefficients
     const int cb = ctx->coef_flip;
     ctx->coef_flip ^= 1;
     SLK_HIP(ctx, hipEventSynchronize(ctx->ev_coef[cb]));  // the copy issued from this buffer two chunks ago (never recorded: returns at once)
-    slk_step_coef *hc = (slk_step_coef *)ctx->h_coef[cb];
-    for (uint32_t m = 0; m < n_mb; ++m) {
-        const double step = (double)(optim->step + 1 + m);
-        slk_step_coef &c = hc[m];
-        c.c0 = c.c1 = 0.0f;
-        if (upd == SLK_EUPD_SGD) {
-            c.c0 = (float)optim->lr;
-        } else if (upd == SLK_EUPD_ADAGRAD || upd == SLK_EUPD_ADAGRAD_DENSE) {
-            c.c0 = (float)(optim->lr / (1.0 + (step - 1.0) * optim->lr_decay));
-        } else {
-            const double bc1 = 1.0 - pow(optim->beta1, step), bc2 = 1.0 - pow(optim->beta2, step);
-            if (upd == SLK_EUPD_SPARSE_ADAM) {
-                c.c0 = (float)(optim->lr * sqrt(bc2) / bc1);
-            } else {
-                c.c0 = (float)(optim->lr / bc1);
-                c.c1 = (float)sqrt(bc2);
-            }
-        }
-    }
-    SLK_HIP(ctx, hipMemcpyAsync(ctx->extra[EP_COEF].p, hc, (size_t)n_mb * sizeof(slk_step_coef), hipMemcpyHostToDevice, s));
+    slk_opt_coef *hc = (slk_opt_coef *)ctx->h_coef[cb];
+    for (uint32_t m = 0; m < n_mb; ++m) hc[m] = slk_opt_coef_at(optim, optim->step + 1 + m);
+    SLK_HIP(ctx, hipMemcpyAsync(ctx->extra[EP_COEF].p, hc, (size_t)n_mb * sizeof(slk_opt_coef), hipMemcpyHostToDevice, s));
     SLK_HIP(ctx, hipEventRecord(ctx->ev_coef[cb], s));
     SLK_HIP(ctx, hipMemsetAsync(ctx->extra[EP_BAR].p, 0, 2048, s));
-    const bool dense_opt = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    const bool dense_opt = slk_opt_is_dense(optim->kind);
     if (dense_opt) {
         const size_t rows = (size_t)tables->num_users + (size_t)tables->num_items;
         SLK_HIP(ctx, hipMemsetAsync(ctx->extra[EP_TOUCH].p, 0, rows * 4, s));
@@ -968,17 +876,13 @@ int slk_epoch_run_chunk(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim
     e.gsn = gsn;
     e.partial = (double *)ctx->extra[EP_PARTIAL].p;
     e.mb_loss = d_mb_loss;
-    e.coef = (const slk_step_coef *)ctx->extra[EP_COEF].p;
+    e.coef = (const slk_opt_coef *)ctx->extra[EP_COEF].p;
     e.touch_u = dense_opt ? (uint32_t *)ctx->extra[EP_TOUCH].p : nullptr;
     e.touch_i = dense_opt ? e.touch_u + tables->num_users : nullptr;
     e.bar = (unsigned *)ctx->extra[EP_BAR].p;
     e.status = &ctx->d_rng->epoch_abort;
     e.loss_kind = loss;
-    e.eps = (float)optim->eps;
-    e.omb1 = (float)(1.0 - optim->beta1);
-    e.omb2 = (float)(1.0 - optim->beta2);
-    e.beta2 = (float)optim->beta2;
-    e.wd = (float)optim->weight_decay;
+    e.hyper = slk_opt_hyper_of(optim);
     // two levels pay above ~128 arrivals (profiles/r02_d_epoch_kernel_anatomy.jsonl: 256 workgroups 9.3 -> 6.0 us per pair)
     e.bar_kind = ctx->opt_epoch_barrier >= 0 ? ctx->opt_epoch_barrier : (grid > 128 ? 1 : 0);
     e.debug = ctx->opt_epoch_debug;

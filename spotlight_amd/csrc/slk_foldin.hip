@@ -20,11 +20,6 @@
 #define SLK_FOLDIN_UNROLL 2         // pair losses: positions per row group whose item rows are in flight together
 #define SLK_FOLDIN_NEG_BATCH 4      // adaptive hinge: candidate rows in flight together
 
-struct slk_foldin_coef {
-    float c0;  // Adagrad (sparse / dense): clr.  SparseAdam: lr * sqrt(bc2) / bc1.  Adam dense: lr / bc1.  SGD: lr
-    float c1;  // Adam dense: sqrt(bc2)
-};
-
 struct slk_foldin_args {
     float *U, *BU;                  // the new users' rows [H][D] and biases [H]
     float *S1U, *S2U, *S1B, *S2B;   // their optimizer state
@@ -36,43 +31,20 @@ struct slk_foldin_args {
     int64_t wg_min;                 // histories of at least this many interactions are the workgroup route's
     uint32_t H;
     int D, nn, loss_kind, kind, nsteps;
-    float eps, omb1, omb2, beta2, wd;
-    slk_foldin_coef c[SLK_FOLDIN_MAX_STEPS];
+    slk_opt_hyper hyper;
+    slk_opt_coef c[SLK_FOLDIN_MAX_STEPS];
 };
 
-// One element's optimizer step: slk_apply_vec (row-sparse Adagrad, SparseAdam, SGD) and k_dense_sweep_all (Adam / Adagrad with
-// weight decay), operation for operation.  The row is touched at every step, so the sparse and the dense forms differ only by
-// weight decay, lr_decay (in c0) and the two Adam roundings.
-__device__ __forceinline__ void slk_foldin_update(const slk_foldin_args &a, const slk_foldin_coef &c, float &p, float &s1, float &s2,
-                                                  float g) {
-    if (a.kind == SLK_OPT_ADAGRAD) {
-        s1 += g * g;
-        p += -c.c0 * (g / (sqrtf(s1) + a.eps));
-    } else if (a.kind == SLK_OPT_SPARSE_ADAM) {
-        const float mu = (g - s1) * a.omb1;
-        const float vu = (g * g - s2) * a.omb2;
-        s1 = mu + s1;
-        s2 = vu + s2;
-        p += -c.c0 * (s1 / (sqrtf(s2) + a.eps));
-    } else if (a.kind == SLK_OPT_SGD) {
-        p += -c.c0 * g;
-    } else if (a.kind == SLK_OPT_ADAM_DENSE) {
-        const float gv = g + a.wd * p;
-        const float m = s1 + a.omb1 * (gv - s1);
-        const float v = s2 * a.beta2 + a.omb2 * (gv * gv);
-        s1 = m;
-        s2 = v;
-        p += -c.c0 * (m / (sqrtf(v) / c.c1 + a.eps));
-    } else {
-        const float gv = g + a.wd * p;
-        const float s = s1 + gv * gv;
-        s1 = s;
-        p += -c.c0 * (gv / (sqrtf(s) + a.eps));
+// One element's optimizer step (slk_opt_step), the kind chosen at run time: one kernel serves all five.
+__device__ __forceinline__ void slk_foldin_step(const slk_foldin_args &a, const slk_opt_coef &c, float &p, float &s1, float &s2, float g) {
+    switch (a.kind) {
+        case SLK_OPT_ADAGRAD: return slk_opt_step<SLK_OPT_ADAGRAD>(a.hyper, c, p, s1, s2, g);
+        case SLK_OPT_SPARSE_ADAM: return slk_opt_step<SLK_OPT_SPARSE_ADAM>(a.hyper, c, p, s1, s2, g);
+        case SLK_OPT_SGD: return slk_opt_step<SLK_OPT_SGD>(a.hyper, c, p, s1, s2, g);
+        case SLK_OPT_ADAM_DENSE: return slk_opt_step<SLK_OPT_ADAM_DENSE>(a.hyper, c, p, s1, s2, g);
+        default: return slk_opt_step<SLK_OPT_ADAGRAD_DENSE>(a.hyper, c, p, s1, s2, g);
     }
 }
-
-__device__ __forceinline__ bool slk_foldin_has_s1(int kind) { return kind != SLK_OPT_SGD; }
-__device__ __forceinline__ bool slk_foldin_has_s2(int kind) { return kind == SLK_OPT_SPARSE_ADAM || kind == SLK_OPT_ADAM_DENSE; }
 
 // One step's pass of ONE row group over its share of the history: positions grp, grp + NGRP, grp + 2 NGRP, ... of the m
 // interactions at `pos` (negatives: neg[r * n + position]).  Every group of the unit makes the same number of trips (the
@@ -205,7 +177,7 @@ __global__ __launch_bounds__(256) void k_foldin_wave(slk_foldin_args a) {
     const int D = a.D;
     const int d0 = gl * VEC;
     const bool on = d0 < D;
-    const bool has1 = slk_foldin_has_s1(a.kind), has2 = slk_foldin_has_s2(a.kind);
+    const bool has1 = slk_opt_has_s1(a.kind), has2 = slk_opt_has_s2(a.kind);
     const size_t uoff = (size_t)user * D + d0;
     slk_vec<VEC> u = on ? slk_vload<VEC>(a.U + uoff) : slk_vzero<VEC>();
     slk_vec<VEC> s1 = (on && has1) ? slk_vload<VEC>(a.S1U + uoff) : slk_vzero<VEC>();
@@ -229,12 +201,12 @@ __global__ __launch_bounds__(256) void k_foldin_wave(slk_foldin_args a) {
             gb += __shfl_xor(gb, mask, 64);
             lacc += __shfl_xor(lacc, mask, 64);
         }
-        const slk_foldin_coef c = a.c[t];
+        const slk_opt_coef c = a.c[t];
         if (on) {  // (a padding lane's elements stay 0: with eps == 0 their update would be 0 / 0)
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) slk_foldin_update(a, c, u.v[i], s1.v[i], s2.v[i], gacc.v[i]);
+            for (int i = 0; i < VEC; ++i) slk_foldin_step(a, c, u.v[i], s1.v[i], s2.v[i], gacc.v[i]);
         }
-        slk_foldin_update(a, c, bu, sb1, sb2, gb);
+        slk_foldin_step(a, c, bu, sb1, sb2, gb);
         if (a.loss && lane64 == 0) a.loss[(size_t)t * a.H + user] = (float)(lacc / (double)m);
     }
     if (grp == 0 && on) {
@@ -267,7 +239,7 @@ __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
     const int D = a.D;
     const int d0 = gl * VEC;
     const bool on = d0 < D;
-    const bool has1 = slk_foldin_has_s1(a.kind), has2 = slk_foldin_has_s2(a.kind);
+    const bool has1 = slk_opt_has_s1(a.kind), has2 = slk_opt_has_s2(a.kind);
     const bool holder = grp == 0;  // the lanes (of wave 0) that keep the row and its state in registers for all steps
     const size_t uoff = (size_t)user * D + d0;
     slk_vec<VEC> p = slk_vzero<VEC>(), s1 = slk_vzero<VEC>(), s2 = slk_vzero<VEC>();
@@ -304,7 +276,7 @@ __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
         }
         __syncthreads();  // every group's part is in LDS (and every thread has read this step's row)
         if (holder) {
-            const slk_foldin_coef c = a.c[t];
+            const slk_opt_coef c = a.c[t];
             slk_vec<VEC> g = slk_vzero<VEC>();
             for (int k = 0; k < GPB; ++k) {  // in group order
                 const slk_vec<VEC> x = slk_vload<VEC>(s_part + k * DL + d0);
@@ -313,7 +285,7 @@ __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
             }
             if (on) {  // (a padding lane's elements stay 0, as in the wave route)
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) slk_foldin_update(a, c, p.v[i], s1.v[i], s2.v[i], g.v[i]);
+                for (int i = 0; i < VEC; ++i) slk_foldin_step(a, c, p.v[i], s1.v[i], s2.v[i], g.v[i]);
             }
             slk_vstore<VEC>(s_u + d0, p);
             if (threadIdx.x == 0) {
@@ -323,7 +295,7 @@ __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
                     gbt += s_gb[k];
                     lt += s_l[k];
                 }
-                slk_foldin_update(a, c, pb, sb1, sb2, gbt);
+                slk_foldin_step(a, c, pb, sb1, sb2, gbt);
                 s_bu = pb;
                 if (a.loss) a.loss[(size_t)t * a.H + user] = (float)(lt / (double)m);
             }
@@ -409,36 +381,14 @@ SLK_EXPORT int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_o
     a.loss_kind = loss;
     a.kind = optim->kind;
     a.wg_min = ctx->opt_foldin_wg_min_len > 0 ? ctx->opt_foldin_wg_min_len : SLK_FOLDIN_WG_MIN_LEN;
-    a.eps = (float)optim->eps;
-    a.omb1 = (float)(1.0 - optim->beta1);
-    a.omb2 = (float)(1.0 - optim->beta2);
-    a.beta2 = (float)optim->beta2;
-    a.wd = (float)optim->weight_decay;
+    a.hyper = slk_opt_hyper_of(optim);
     const unsigned wave_grid = (unsigned)((n_new_users + 3) / 4), wg_grid = (unsigned)n_new_users;
     for (int64_t t0 = 0; t0 < n_steps; t0 += SLK_FOLDIN_MAX_STEPS) {
         const int ns = (int)(n_steps - t0 < SLK_FOLDIN_MAX_STEPS ? n_steps - t0 : SLK_FOLDIN_MAX_STEPS);
         a.nsteps = ns;
         a.neg = d_neg ? d_neg + (size_t)t0 * (size_t)nn * (size_t)n : nullptr;
         a.loss = d_loss ? d_loss + (size_t)t0 * (size_t)n_new_users : nullptr;
-        // per-step coefficients, in double like torch (slk_set_opt_coeffs / slk_dense_sweeps)
-        for (int t = 0; t < ns; ++t) {
-            const double step = (double)(optim->step + t0 + t + 1);
-            slk_foldin_coef &c = a.c[t];
-            c.c0 = c.c1 = 0.0f;
-            if (optim->kind == SLK_OPT_SGD) {
-                c.c0 = (float)optim->lr;
-            } else if (optim->kind == SLK_OPT_ADAGRAD || optim->kind == SLK_OPT_ADAGRAD_DENSE) {
-                c.c0 = (float)(optim->lr / (1.0 + (step - 1.0) * optim->lr_decay));
-            } else {
-                const double bc1 = 1.0 - pow(optim->beta1, step), bc2 = 1.0 - pow(optim->beta2, step);
-                if (optim->kind == SLK_OPT_SPARSE_ADAM) {
-                    c.c0 = (float)(optim->lr * sqrt(bc2) / bc1);
-                } else {
-                    c.c0 = (float)(optim->lr / bc1);
-                    c.c1 = (float)sqrt(bc2);
-                }
-            }
-        }
+        for (int t = 0; t < ns; ++t) a.c[t] = slk_opt_coef_at(optim, optim->step + t0 + t + 1);
         // long histories first: they are the launch's tail
         hipLaunchKernelGGL(wg_fn, dim3(wg_grid), dim3(256), 0, call.s, a);
         SLK_LAUNCH_CHECK(ctx, "k_foldin_wg");

@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "slk_common.h"
+#include "slk_optim.h"
 
 // ---------------------------------------------------------------------------------------
 // BloomEmbedding (spotlight/layers.py:74-244): the vector of id x is the sum of n_hash rows
@@ -145,10 +146,8 @@ struct slk_pass_args {
     const float *vrows;      // slot -> item row (D floats) + bias
     float *grows;            // slot -> g * u_old (D floats) + g
     const uint32_t *vslot;   // [pos*NP + s] -> slot
-    // optimizer coefficients, rounded from double on the host exactly as torch does
-    float c_lr;    // Adagrad: clr.  SparseAdam: step_size.
-    float c_eps;
-    float c_omb1, c_omb2;  // 1-beta1, 1-beta2
+    slk_opt_coef coef;     // this step's optimizer coefficients and hyper-parameters (slk_optim.h)
+    slk_opt_hyper hyper;
     int nt;                // cache-policy bits (ctx option "nt")
     int ubz;               // 1: the user biases are identically zero and this pass cannot change them (slk_tables::flags): not fetched
     // user-row ping-pong of a training scope (slk_user_pingpong_begin, pair mode over a plain user table): the user table
@@ -166,11 +165,14 @@ struct slk_pass_args {
     const uint8_t *msorted;
 };
 
+// Row-update mode of the fused passes: the row-sparse optimizers' rule in place, or GRAD_ONLY -- the *_DENSE optimizers' summed
+// gradient goes to the dense gradient buffer (aliased on S1) and k_dense_sweep_all applies the rule to every row.
 enum { SLK_UPD_ADAGRAD = 0, SLK_UPD_SPARSE_ADAM = 1, SLK_UPD_GRAD_ONLY = 2, SLK_UPD_SGD = 3 };
-// a zero summed gradient leaves the row exactly as it is (no write needed): Adagrad (sum += 0, p -= 0) and SGD (p -= 0)
-#define SLK_UPD_ZERO_IS_NOOP(UPD) ((UPD) == SLK_UPD_ADAGRAD || (UPD) == SLK_UPD_SGD)
-// the row update reads first-state rows (S1): not SGD (stateless), not GRAD_ONLY (S1 is the gradient buffer it writes)
-#define SLK_UPD_HAS_STATE(UPD) ((UPD) == SLK_UPD_ADAGRAD || (UPD) == SLK_UPD_SPARSE_ADAM)
+// the optimizer kind whose rule (and predicates: slk_optim.h) a mode applies; GRAD_ONLY applies none
+constexpr int slk_upd_kind(int upd) {
+    return upd == SLK_UPD_ADAGRAD ? SLK_OPT_ADAGRAD
+                                  : (upd == SLK_UPD_SPARSE_ADAM ? SLK_OPT_SPARSE_ADAM : (upd == SLK_UPD_SGD ? SLK_OPT_SGD : SLK_OPT_NONE));
+}
 
 // How the item pass turns an occurrence payload r into a gradient contribution:
 //   SNAP  r = pos*NP + s; record(pos) = [u_old (D)], g_s = gsn[r - begin*NP];  vec = g_s * u_old, bias g_s
@@ -201,53 +203,44 @@ __device__ __forceinline__ size_t slk_blk_scalar(uint32_t slot, int D) {
 // index of item i's bias (and of its optimizer state) in P[3] / S1[3] / S2[3]
 #define SLK_B3(a_, i_) ((size_t)(i_) << (a_).bsh3)
 
-// Row update for the elements one lane owns.  GRAD_ONLY stores the summed gradient into the
-// dense gradient buffer (aliased on S1) for the full-table sweep.
+// Row update for the elements one lane owns, the parameter / first-state elements already in registers (loaded early, see
+// k_item_pass): the optimizer's rule (slk_opt_step) and its stores.  GRAD_ONLY is no rule: it stores the summed gradient into
+// the dense gradient buffer (aliased on S1) for the full-table sweep.
+template <int VEC, int UPD, bool S2PRE = false>
+__device__ __forceinline__ void slk_apply_vec_pre(const slk_pass_args &a, int t, size_t off, slk_vec<VEC> &p,
+                                                  slk_vec<VEC> &s, const slk_vec<VEC> &g,
+                                                  const slk_vec<VEC> *s2 = nullptr, bool nt = false, float *pdst = nullptr) {
+    if constexpr (UPD == SLK_UPD_GRAD_ONLY) {
+        slk_vstore<VEC>(a.S1[t] + off, g);
+    } else {
+        constexpr int KIND = slk_upd_kind(UPD);
+        // pdst: where the updated parameter elements go (user-row ping-pong: the other copy of the table); default in place
+        float *const pout = pdst ? pdst : a.P[t] + off;
+        slk_vec<VEC> v = slk_vzero<VEC>();
+        if (slk_opt_has_s2(KIND)) v = S2PRE ? *s2 : slk_vload<VEC>(a.S2[t] + off);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) slk_opt_step<KIND>(a.hyper, a.coef, p.v[i], s.v[i], v.v[i], g.v[i]);
+        if (slk_opt_has_s1(KIND)) slk_vstore_if_nt<VEC>(a.S1[t] + off, s, nt);
+        if (slk_opt_has_s2(KIND)) slk_vstore_if_nt<VEC>(a.S2[t] + off, v, nt);
+        slk_vstore_if_nt<VEC>(pout, p, nt);
+    }
+}
+
+// The same with the state still in memory: loaded here, under the caller's cache policy.
 template <int VEC, int UPD>
 __device__ __forceinline__ void slk_apply_vec(const slk_pass_args &a, int t, size_t off, slk_vec<VEC> &p,
                                               const slk_vec<VEC> &g, bool nt = false, float *pdst = nullptr) {
-    // pdst: where the updated parameter elements go (user-row ping-pong: the other copy of the table); default in place
-    float *const pout = pdst ? pdst : a.P[t] + off;
-    if (UPD == SLK_UPD_ADAGRAD) {
-        // torch/optim/adagrad.py:360-385: sum += g^2; p += -clr * (g / (sqrt(sum) + eps))
-        slk_vec<VEC> s = slk_vload_if_nt<VEC>(a.S1[t] + off, nt);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            s.v[i] += g.v[i] * g.v[i];
-            p.v[i] += -a.c_lr * (g.v[i] / (sqrtf(s.v[i]) + a.c_eps));
-        }
-        slk_vstore_if_nt<VEC>(a.S1[t] + off, s, nt);
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else if (UPD == SLK_UPD_SPARSE_ADAM) {
-        // torch/optim/_functional.py:61-84
-        slk_vec<VEC> m = slk_vload_if_nt<VEC>(a.S1[t] + off, nt);
-        slk_vec<VEC> v = slk_vload_if_nt<VEC>(a.S2[t] + off, nt);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const float mu = (g.v[i] - m.v[i]) * a.c_omb1;
-            const float vu = (g.v[i] * g.v[i] - v.v[i]) * a.c_omb2;
-            m.v[i] = mu + m.v[i];
-            v.v[i] = vu + v.v[i];
-            p.v[i] += -a.c_lr * (m.v[i] / (sqrtf(v.v[i]) + a.c_eps));
-        }
-        slk_vstore_if_nt<VEC>(a.S1[t] + off, m, nt);
-        slk_vstore_if_nt<VEC>(a.S2[t] + off, v, nt);
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else if (UPD == SLK_UPD_SGD) {
-        // torch/optim/sgd.py (momentum 0, weight_decay 0): param.add_(grad, alpha=-lr)
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) p.v[i] += -a.c_lr * g.v[i];
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else {
-        slk_vstore<VEC>(a.S1[t] + off, g);
-    }
+    slk_vec<VEC> s = slk_vzero<VEC>(), s2 = s;
+    if (slk_opt_has_s1(slk_upd_kind(UPD))) s = slk_vload_if_nt<VEC>(a.S1[t] + off, nt);
+    if (slk_opt_has_s2(slk_upd_kind(UPD))) s2 = slk_vload_if_nt<VEC>(a.S2[t] + off, nt);
+    slk_apply_vec_pre<VEC, UPD, true>(a, t, off, p, s, g, &s2, nt, pdst);
 }
 
 template <int UPD>
 __device__ __forceinline__ void slk_apply_bias(const slk_pass_args &a, int t, size_t row, float g) {
     slk_vec<1> gv;
     gv.v[0] = g;
-    if (SLK_UPD_ZERO_IS_NOOP(UPD) && g == 0.0f) return;  // exact no-op: sum += 0, p -= 0
+    if (slk_opt_zero_is_noop(slk_upd_kind(UPD)) && g == 0.0f) return;  // exact no-op: sum += 0, p -= 0
     slk_vec<1> p = slk_vload<1>(a.P[t] + row);
     slk_apply_vec<1, UPD>(a, t, row, p, gv);
 }
@@ -401,43 +394,6 @@ enum { SLK_PART_BOTH = 0, SLK_PART_ROWS = 1, SLK_PART_BIAS = 2 };
                            // at 7: C3 1.78 -> 1.81 ms, C4 0.55 -> 0.61, C2 item pass 0.296 -> 0.310, profiles/r03_zf_*)
 #endif
 
-// Row update with the parameter / first-state elements already in registers (loaded early, see
-// k_item_pass).  Same arithmetic, in the same order, as slk_apply_vec.
-template <int VEC, int UPD, bool S2PRE = false>
-__device__ __forceinline__ void slk_apply_vec_pre(const slk_pass_args &a, int t, size_t off, slk_vec<VEC> &p,
-                                                  slk_vec<VEC> &s, const slk_vec<VEC> &g,
-                                                  const slk_vec<VEC> *s2 = nullptr, bool nt = false, float *pdst = nullptr) {
-    float *const pout = pdst ? pdst : a.P[t] + off;
-    if (UPD == SLK_UPD_ADAGRAD) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            s.v[i] += g.v[i] * g.v[i];
-            p.v[i] += -a.c_lr * (g.v[i] / (sqrtf(s.v[i]) + a.c_eps));
-        }
-        slk_vstore_if_nt<VEC>(a.S1[t] + off, s, nt);
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else if (UPD == SLK_UPD_SPARSE_ADAM) {
-        slk_vec<VEC> v = S2PRE ? *s2 : slk_vload<VEC>(a.S2[t] + off);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const float mu = (g.v[i] - s.v[i]) * a.c_omb1;
-            const float vu = (g.v[i] * g.v[i] - v.v[i]) * a.c_omb2;
-            s.v[i] = mu + s.v[i];
-            v.v[i] = vu + v.v[i];
-            p.v[i] += -a.c_lr * (s.v[i] / (sqrtf(v.v[i]) + a.c_eps));
-        }
-        slk_vstore_if_nt<VEC>(a.S1[t] + off, s, nt);
-        slk_vstore_if_nt<VEC>(a.S2[t] + off, v, nt);
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else if (UPD == SLK_UPD_SGD) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) p.v[i] += -a.c_lr * g.v[i];
-        slk_vstore_if_nt<VEC>(pout, p, nt);
-    } else {
-        slk_vstore<VEC>(a.S1[t] + off, g);
-    }
-}
-
 // flags of a partial (slk_pass_args::ipart_meta[slot][1])
 enum { SLK_IPART_STARTS = 2, SLK_IPART_ENDS = 4, SLK_IPART_ANY = 8, SLK_IPART_GEN_SHIFT = 4 };  // flags | launch stamp << 4
 
@@ -452,19 +408,19 @@ __device__ __forceinline__ void slk_item_apply(const slk_pass_args &a, uint32_t 
     if (rows_on) {
         if (!pre && UPD != SLK_UPD_GRAD_ONLY) {
             p = slk_vload_if_nt<VEC>(a.P[1] + voff, nt_rows);
-            if (SLK_UPD_HAS_STATE(UPD)) s = slk_vload_if_nt<VEC>(a.S1[1] + voff, nt_rows);
+            if (slk_opt_has_s1(slk_upd_kind(UPD))) s = slk_vload_if_nt<VEC>(a.S1[1] + voff, nt_rows);
         }
         slk_apply_vec_pre<VEC, UPD>(a, 1, voff, p, s, gv, nullptr, nt_rows);
     }
     if (lane == 0 && PART != SLK_PART_ROWS) {
-        if (SLK_UPD_ZERO_IS_NOOP(UPD) && gb == 0.0f) return;  // exact no-op
+        if (slk_opt_zero_is_noop(slk_upd_kind(UPD)) && gb == 0.0f) return;  // exact no-op
         slk_vec<1> bpv, bsv, gbv;
         if (pre || UPD == SLK_UPD_GRAD_ONLY) {
             bpv.v[0] = bp;
             bsv.v[0] = bs;
         } else {
             bpv.v[0] = a.P[3][SLK_B3(a, item)];
-            bsv.v[0] = SLK_UPD_HAS_STATE(UPD) ? a.S1[3][SLK_B3(a, item)] : 0.0f;
+            bsv.v[0] = slk_opt_has_s1(slk_upd_kind(UPD)) ? a.S1[3][SLK_B3(a, item)] : 0.0f;
         }
         gbv.v[0] = gb;
         slk_apply_vec_pre<1, UPD>(a, 3, SLK_B3(a, item), bpv, bsv, gbv);
@@ -641,11 +597,11 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(NPRE_ > SLK_ITEM_NPRE ? 4 : S
                 if (rows_on && UPD != SLK_UPD_GRAD_ONLY) {
                     const size_t voff = (size_t)item * D + d0;
                     pv[h] = slk_vload_if_nt<VEC>(a.P[1] + voff, nt_rows);
-                    if (SLK_UPD_HAS_STATE(UPD)) sv[h] = slk_vload_if_nt<VEC>(a.S1[1] + voff, nt_rows);
+                    if (slk_opt_has_s1(slk_upd_kind(UPD))) sv[h] = slk_vload_if_nt<VEC>(a.S1[1] + voff, nt_rows);
                 }
                 if (PART != SLK_PART_ROWS && UPD != SLK_UPD_GRAD_ONLY) {
                     pb[h] = a.P[3][SLK_B3(a, item)];
-                    if (SLK_UPD_HAS_STATE(UPD)) sb[h] = a.S1[3][SLK_B3(a, item)];
+                    if (slk_opt_has_s1(slk_upd_kind(UPD))) sb[h] = a.S1[3][SLK_B3(a, item)];
                 }
             }
         }
@@ -1175,20 +1131,11 @@ static inline int slk_upd_for(int opt_kind) {
     return SLK_UPD_GRAD_ONLY;
 }
 
-// Per-step optimizer coefficients, formed in double and rounded to fp32 as torch does.
+// This step's optimizer coefficients (slk_optim.h) for a launch of the fused passes.
 static inline void slk_set_opt_coeffs(slk_pass_args &a, const slk_optim *optim) {
-    const double step = (double)(optim->step + 1);
-    a.c_eps = (float)optim->eps;
-    if (optim->kind == SLK_OPT_SGD) {
-        a.c_lr = (float)optim->lr;
-    } else if (optim->kind == SLK_OPT_ADAGRAD) {
-        a.c_lr = (float)(optim->lr / (1.0 + (step - 1.0) * optim->lr_decay));
-    } else if (optim->kind == SLK_OPT_SPARSE_ADAM) {
-        const double bc1 = 1.0 - pow(optim->beta1, step), bc2 = 1.0 - pow(optim->beta2, step);
-        a.c_lr = (float)(optim->lr * sqrt(bc2) / bc1);
-        a.c_omb1 = (float)(1.0 - optim->beta1);
-        a.c_omb2 = (float)(1.0 - optim->beta2);
-    }
+    if (slk_opt_is_dense(optim->kind)) return;  // GRAD_ONLY passes read none: the sweep has its own (slk_dense_sweeps)
+    a.coef = slk_opt_coef_at(optim, optim->step + 1);
+    a.hyper = slk_opt_hyper_of(optim);
 }
 
 // slk_bilinear.hip: validates the optimizer block (kinds, state pointers for tables in `mask`)

@@ -679,7 +679,7 @@ static int poolnet_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim 
     if ((rc = slk_ensure(ctx, ctx->extra[SQ_GSN], (size_t)bsz * L * NP * 4))) return rc;  // dL/dscore per (timestep, pair)
     const unsigned max_grid = (unsigned)ctx->num_cus * 8;
     if ((rc = slk_ensure(ctx, ctx->losspart, (size_t)max_grid * 8))) return rc;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    const bool dense = slk_opt_is_dense(optim->kind);
     if (dense) {
         const size_t elems[4] = {0, (size_t)(Hi ? ibd.rows : tables->num_items) * D, 0, (size_t)tables->num_items};
         if ((rc = slk_ensure_dgrad(ctx, elems, TM, s))) return rc;

@@ -731,7 +731,7 @@ SLK_EXPORT int slk_shard_user_pass(slk_ctx *ctx, const slk_tables *local, const 
     SLK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     ctx->last_stream = s;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    const bool dense = slk_opt_is_dense(optim->kind);
     if (dense) {
         const size_t elems[4] = {(size_t)local->num_users * local->dim, (size_t)local->num_items * local->dim,
                                  (size_t)local->num_users, (size_t)local->num_items};
@@ -753,7 +753,7 @@ SLK_EXPORT int slk_shard_user_pass(slk_ctx *ctx, const slk_tables *local, const 
     a.loss_kind = loss;
     a.inv_b = 1.0f / (float)global_batch;
     a.ubz = (local->flags & SLK_TABLES_USER_BIAS_ZERO) && (loss == SLK_LOSS_BPR || loss == SLK_LOSS_HINGE) &&
-            (optim->kind == SLK_OPT_ADAGRAD || optim->kind == SLK_OPT_SGD) && ctx->opt_user_bias_zero_hint;
+            slk_opt_zero_is_noop(optim->kind) && ctx->opt_user_bias_zero_hint;
     const unsigned gpb = 256u / (unsigned)g;
     slk_pass_fn upass = nullptr;
     const int upd = slk_upd_for(optim->kind);
@@ -871,7 +871,7 @@ SLK_EXPORT int slk_shard_user_pass_adaptive(slk_ctx *ctx, const slk_tables *loca
     SLK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     ctx->last_stream = s;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    const bool dense = slk_opt_is_dense(optim->kind);
     if (dense) {
         const size_t elems[4] = {(size_t)local->num_users * local->dim, (size_t)local->num_items * local->dim,
                                  (size_t)local->num_users, (size_t)local->num_items};
@@ -911,7 +911,7 @@ SLK_EXPORT int slk_shard_item_pass(slk_ctx *ctx, const slk_tables *local, slk_op
     SLK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
     ctx->last_stream = s;
-    const bool dense = optim->kind == SLK_OPT_ADAM_DENSE || optim->kind == SLK_OPT_ADAGRAD_DENSE;
+    const bool dense = slk_opt_is_dense(optim->kind);
     const bool shadowed = ctx->shadow_active && ctx->shadow_src_p == local->d_param[3];
     if (shadowed && (optim->kind != SLK_OPT_ADAGRAD || optim->d_state1[3] != ctx->shadow_src_s))
         return slk_fail(ctx, SLK_EINVAL, "slk_shard_item_pass: the item biases are shadowed (slk_bias_shadow_begin) for another optimizer state");
