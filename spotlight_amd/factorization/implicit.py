@@ -4,6 +4,8 @@ Same constructor, fit(), predict(), error messages and random-state behaviour as
 reference; everything inside the epoch loop (negative sampling, both forward passes, loss,
 backward, optimizer update) is one C-ABI call into csrc/libspotlight_hip.so per epoch.
 """
+import inspect
+
 import numpy as np
 import torch
 import torch.optim as optim
@@ -105,6 +107,27 @@ def _reject_negative_ids(ids):
         raise IndexError('index out of range in self')
 
 
+# param-group keys that select an implementation of the same arithmetic (torch/optim/optimizer.py), never another rule
+_ARITHMETIC_NEUTRAL_KEYS = ('foreach', 'fused', 'capturable', 'differentiable')
+
+
+def _refuse_unread_options(optimizer, group, read):
+    """A param-group key that the binding neither reads (`read`) nor knows to be arithmetic-neutral, set to something
+    else than the optimizer class's own default, asks for a rule the fused update does not have: NotImplementedError, so
+    that fit() takes the autograd route with the real torch optimizer instead of silently ignoring the option.
+    LIMITATION: the defaults are those of type(optimizer).__init__'s signature.  A key that signature does not name has no
+    default to differ from and is skipped: a scheduler's 'initial_lr' (rightly), but also an option that a subclass of
+    Adagrad / SparseAdam takes through **kwargs and writes into its param groups -- such a subclass is bound as its base class."""
+    defaults = inspect.signature(type(optimizer).__init__).parameters
+    for key, value in group.items():
+        if key == 'params' or key in read or key in _ARITHMETIC_NEUTRAL_KEYS or key not in defaults:
+            continue
+        default = defaults[key].default
+        same = (value is default) or (not torch.is_tensor(value) and not torch.is_tensor(default) and value == default)
+        if not same:
+            raise NotImplementedError('{}({}={!r}) has no fused gfx950 update'.format(type(optimizer).__name__, key, value))
+
+
 class _OptimizerBinding(object):
     """Maps a torch.optim object onto slk_optim.  The torch optimizer stays the owner of
     hyper-parameters and state tensors (so state_dict / pickle / resuming fit() behave as
@@ -125,6 +148,8 @@ class _OptimizerBinding(object):
             if sparse and wd != 0:
                 # torch/optim/adagrad.py:355-358
                 raise RuntimeError('weight_decay option is not compatible with sparse gradients')
+            # (initial_accumulator_value is already in state['sum'], torch/optim/adagrad.py:80-90)
+            _refuse_unread_options(optimizer, g, ('lr', 'eps', 'weight_decay', 'lr_decay', 'initial_accumulator_value', 'maximize'))
             self.kind = 'adagrad_dense' if wd != 0 else 'adagrad'
             self.hp = dict(lr=g['lr'], eps=g['eps'], weight_decay=wd, lr_decay=g['lr_decay'])
             self.s1 = [st[p]['sum'] for p in params]
@@ -133,6 +158,7 @@ class _OptimizerBinding(object):
             if not sparse:
                 raise RuntimeError('SparseAdam does not support dense gradients, please consider '
                                    'Adam instead')
+            _refuse_unread_options(optimizer, g, ('lr', 'eps', 'betas', 'maximize'))
             self.kind = 'sparse_adam'
             self.hp = dict(lr=g['lr'], eps=g['eps'], betas=g['betas'])
             for p in params:
@@ -145,6 +171,10 @@ class _OptimizerBinding(object):
                                    'SparseAdam instead')
             if g.get('amsgrad', False):
                 raise NotImplementedError('amsgrad=True is not supported')
+            if g.get('decoupled_weight_decay', False) and g['weight_decay'] != 0:
+                # AdamW's rule, p *= 1 - lr * wd (torch/optim/adam.py); the fused update adds wd * p to the gradient
+                raise NotImplementedError('decoupled_weight_decay=True with a non-zero weight_decay is not supported')
+            _refuse_unread_options(optimizer, g, ('lr', 'eps', 'betas', 'weight_decay', 'amsgrad', 'maximize', 'decoupled_weight_decay'))
             self.kind = 'adam_dense'
             self.hp = dict(lr=g['lr'], eps=g['eps'], betas=g['betas'], weight_decay=g['weight_decay'])
             for p in params:
@@ -159,6 +189,8 @@ class _OptimizerBinding(object):
             if g.get('momentum', 0) != 0 or g.get('weight_decay', 0) != 0 or g.get('nesterov', False):
                 raise NotImplementedError('torch.optim.SGD has a fused gfx950 update only with momentum=0, weight_decay=0, '
                                           'nesterov=False')
+            # (dampening scales the gradient's share of a momentum buffer: without momentum there is none)
+            _refuse_unread_options(optimizer, g, ('lr', 'momentum', 'dampening', 'weight_decay', 'nesterov', 'maximize'))
             self.kind = 'sgd'
             self.hp = dict(lr=g['lr'])
             self.s1 = None

@@ -928,11 +928,13 @@ BLOOM_FIXTURES = ['bloom_item_bpr_adagrad', 'bloom_item_adaptive_hinge_adam_defa
 
 
 def check_chunking_is_bit_neutral(be, loss, opt, D, U=3000, I=1000, N=30000, B=1000, nn=5, user_bloom=0, item_bloom=0,
-                                  chunk=4096, overlap=1, seed=21, nt=None):
+                                  chunk=4096, overlap=1, seed=21, nt=None, hp=None, step0=0):
     """The engine is deterministic (sorted ownership, no atomics), and chunking / the prep pipeline
     only change WHEN value-independent work happens: one big chunk on one stream and many small
     chunks with prep on the second stream must agree bit for bit -- losses, negatives, every table,
-    every optimizer-state tensor and the final RNG state."""
+    every optimizer-state tensor and the final RNG state.
+    `hp`: the optimizer's hyper-parameters in place of lr = 0.05 and defaults; `step0`: steps already taken."""
+    hp = dict(lr=0.05) if hp is None else hp
     eng = be.engine
     rs = np.random.RandomState(seed)
     users = rs.randint(0, U, N).astype(np.int64)
@@ -949,7 +951,8 @@ def check_chunking_is_bit_neutral(be, loss, opt, D, U=3000, I=1000, N=30000, B=1
         if nt is not None and chunk_i == chunk:  # the second run also uses another cache policy
             eng.set_option('nt', nt)
         try:
-            dev = be.model(params, opt=opt, lr=0.05, user_bloom=ud, item_bloom=idesc)
+            dev = be.model(params, opt=opt, user_bloom=ud, item_bloom=idesc, **hp)
+            dev.optim.step = step0
             eng.rng_set_state(state)
             d_users, d_items = be.alloc(users), be.alloc(items)
             mb_loss = be.alloc(np.zeros(n_mb, dtype=np.float32))
@@ -957,6 +960,7 @@ def check_chunking_is_bit_neutral(be, loss, opt, D, U=3000, I=1000, N=30000, B=1
             for _ in range(2):
                 eng.bilinear_train(dev.tables, dev.optim, be.ptr(d_users), be.ptr(d_items), N, B, loss, nn,
                                    be.ptr(mb_loss), d_neg_out=be.ptr(neg_out), stream=be.stream)
+            assert dev.optim.step == step0 + 2 * n_mb
             st = eng.rng_get_state()
             results.append([be.get(mb_loss), be.get(neg_out), st[1], np.array(st[2])] +
                            [be.get(x) for x in dev.p + dev.s1 + dev.s2])
@@ -1488,13 +1492,16 @@ def check_bias_shadow_is_bit_neutral(be, loss, D, U, I, N, B, nn=1, seed=43, opt
     assert not np.array_equal(results[0][4].ravel(), params[3].astype(np.float32).ravel())  # (the biases did train)
 
 
-def check_user_pingpong_is_bit_neutral(be, loss, opt, D, U, I, N, B, seed=53, options=None, with_bias_shadow=False, calls=2, sanity=True):
+def check_user_pingpong_is_bit_neutral(be, loss, opt, D, U, I, N, B, seed=53, options=None, with_bias_shadow=False, calls=2, sanity=True,
+                                       hp=None, step0=0):
     """Training inside a user-row ping-pong scope (slk_user_pingpong_begin / _end: the user table doubled in the ctx, the user
     pass writes updated rows to the other copy and no record, the item pass gathers pre-step rows where they still stand)
     against plain training: losses, every table and state tensor bit for bit.  Inside the scope the caller's user table is a MIX
     of rows (some current rows live in the ctx's copy); the scope's end makes it whole.  `calls` training calls per scope: a
     user's current copy alternates with every minibatch that touches it.  `sanity=False` (the fuzz: one-item tables, single
-    interactions): the "something did train" asserts are skipped, the bit-for-bit ones are not."""
+    interactions): the "something did train" asserts are skipped, the bit-for-bit ones are not.
+    `hp`: the optimizer's hyper-parameters in place of lr = 0.05 and defaults; `step0`: steps already taken."""
+    hp = dict(lr=0.05) if hp is None else hp
     eng = be.engine
     rs = np.random.RandomState(seed)
     users = rs.randint(0, U, N).astype(np.int64)
@@ -1509,7 +1516,8 @@ def check_user_pingpong_is_bit_neutral(be, loss, opt, D, U, I, N, B, seed=53, op
         for k, v in (options or {}).items():
             eng.set_option(k, v)
         try:
-            dev = be.model(params, opt=opt, lr=0.05)
+            dev = be.model(params, opt=opt, **hp)
+            dev.optim.step = step0
             eng.rng_set_state(state)
             d_users, d_items = be.alloc(users), be.alloc(items)
             mb_loss = be.alloc(np.zeros(calls * n_mb, dtype=np.float32))
@@ -1522,6 +1530,7 @@ def check_user_pingpong_is_bit_neutral(be, loss, opt, D, U, I, N, B, seed=53, op
                     if pingpong:
                         assert eng.get_stat('pingpong_calls') == n0 + calls, 'a call of the scope did not run on the two copies'
                         mixed = be.get(dev.p[0]).copy()
+            assert dev.optim.step == step0 + calls * n_mb
             results.append([be.get(mb_loss)] + [be.get(x) for x in dev.p + dev.s1 + dev.s2])
         finally:
             for k, v in saved.items():
@@ -1660,18 +1669,22 @@ def check_user_pingpong_contract(be):
 # persistent epoch kernel (csrc/slk_epoch.hip) against the per-minibatch launches
 # ---------------------------------------------------------------------------------------
 def check_epoch_kernel_is_bit_identical(be, loss, opt, D, U=300, I=170, N=2500, B=256, seed=31, chunk=None, epochs=2,
-                                        max_grid=None, barrier=-1, cooperative=0, nn=None):
+                                        max_grid=None, barrier=-1, cooperative=0, nn=None, hp=None, step0=0):
     """The persistent route (option epoch_kernel = 1: every minibatch of a chunk in one cooperative launch) performs the
     launch path's arithmetic in the launch path's order: losses to fp32 summation-order noise, negatives, RNG state and
     EVERY table / optimizer-state tensor bit for bit -- including the dense optimizers, whose full-table sweep the
-    persistent route folds into the gaps between the owned rows."""
+    persistent route folds into the gaps between the owned rows.
+    `hp`: the optimizer's hyper-parameters in place of lr = 0.05 (dense kinds: weight_decay = 1e-3) and defaults; `step0`: steps
+    already taken (with lr_decay, or bias corrections that have not converged, every minibatch of a chunk has its own
+    coefficients: the persistent kernel's table hc[m])."""
     eng = be.engine
     rs = np.random.RandomState(seed)
     users = rs.randint(0, U, N).astype(np.int64)
     items = rs.randint(0, I, N).astype(np.int64)
     sc = min(0.3, 1.0 / np.sqrt(D))
     params = [rs.normal(0, sc, (U, D)), rs.normal(0, sc, (I, D)), rs.normal(0, 0.1, U), rs.normal(0, 0.1, I)]
-    hp = dict(lr=0.05, weight_decay=1e-3 if opt.endswith('dense') else 0.0)
+    if hp is None:
+        hp = dict(lr=0.05, weight_decay=1e-3 if opt.endswith('dense') else 0.0)
     state = np.random.RandomState(seed + 1).get_state()
     n_mb = (N + B - 1) // B
     # explicit feedback (ExplicitFactorizationModel.fit, factorization/explicit.py:213-236): one pair per interaction,
@@ -1694,6 +1707,7 @@ def check_epoch_kernel_is_bit_identical(be, loss, opt, D, U=300, I=170, N=2500, 
         eng.set_option('epoch_cooperative', cooperative)
         try:
             dev = be.model(params, opt=opt, **hp)
+            dev.optim.step = step0
             eng.rng_set_state(state)
             d_users, d_items = be.alloc(users), be.alloc(items)
             d_ratings = be.alloc(ratings) if explicit else None
@@ -1718,7 +1732,7 @@ def check_epoch_kernel_is_bit_identical(be, loss, opt, D, U=300, I=170, N=2500, 
             else:
                 assert prof['epoch'][0] == 0 and prof['user_pass'][0] == epochs * n_mb, prof
             st = eng.rng_get_state()
-            assert dev.optim.step == epochs * n_mb
+            assert dev.optim.step == step0 + epochs * n_mb
             results.append((np.concatenate(losses), [be.get(neg_out), st[1], np.array(st[2])] +
                             [be.get(x) for x in dev.p + dev.s1 + dev.s2]))
         finally:

@@ -95,7 +95,7 @@ class Fold(object):
     """Device side of a Problem: the new rows + their state in slots 0 / 2, the model's item tables in 1 / 3, and
     sentinel-filled buffers as optimizer state of the item tables (never read, never written)."""
 
-    def __init__(self, be, pr, opt, state=None, step=0):
+    def __init__(self, be, pr, opt, state=None, step=0, hp=None):
         f32 = lambda x: be.alloc(np.array(x, dtype=np.float32, order='C'))
         self.be = be
         self.p = [f32(pr.U), f32(pr.V), f32(pr.b), f32(pr.bi)]
@@ -105,7 +105,8 @@ class Fold(object):
         self.s1 = [f32(s[0]), sent(), f32(s[1]), sent()]
         self.s2 = [f32(s[2]), sent(), f32(s[3]), sent()]
         self.tables = _native.make_tables([be.ptr(x) for x in self.p], pr.H, pr.I, pr.D)
-        self.optim = _native.make_optim(opt, [be.ptr(x) for x in self.s1], [be.ptr(x) for x in self.s2], step=step, **hparams(opt))
+        self.optim = _native.make_optim(opt, [be.ptr(x) for x in self.s1], [be.ptr(x) for x in self.s2], step=step,
+                                        **(hparams(opt) if hp is None else hp))
         self.d_off, self.d_items = be.alloc(pr.off), be.alloc(pr.items if pr.n else np.zeros(1, np.int64))
         self.pr = pr
 
