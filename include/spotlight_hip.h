@@ -206,7 +206,10 @@ const char *slk_last_error(const slk_ctx *ctx); /* ctx may be NULL: last create 
  *   "foldin_wg_min_len"   slk_bilinear_foldin: histories of at least this many interactions take the workgroup route (one
  *                         256-thread workgroup per user), shorter ones the wave route (one wavefront per user); 0, the default:
  *                         the measured crossover.  A test and measurement switch, and like "adaptive_late_min_batch" NOT
- *                         bit-neutral: the two routes add a user's gradient terms in different (each fixed) orders */
+ *                         bit-neutral: the two routes add a user's gradient terms in different (each fixed) orders
+ *   "weighted_max_values" slk_sample_items_weighted: values one internal draw produces (default 2^27: 1 GiB of generated words;
+ *                         at most 312 * (2^31 - 2), the generator's block limit); a larger count is a run of consecutive
+ *                         draws.  A test and measurement switch: ids and final state are the same under every value */
 int slk_ctx_set_option(slk_ctx *ctx, const char *name, int64_t value);
 /* The current value of an option (ABI 9): lets a caller change an option for one piece of work and restore it afterwards --
  * a ctx is shared by every model of a process on its device (spotlight_amd/_native.py: `with engine.options(...)`). */
@@ -247,6 +250,33 @@ int slk_rng_get_state_sampled(slk_ctx *ctx, uint32_t *h_key, int32_t *pos);
  * ids in [0, num_items) by numpy's masked rejection over the ctx's MT19937 stream,
  * bit-exact, written row-major as int64 to d_out.  1 <= num_items <= 2^32. */
 int slk_sample_items(slk_ctx *ctx, int64_t num_items, int64_t count, int64_t *d_out, void *stream);
+
+/* Weighted sampling (added to ABI 14: three new entries, nothing existing changes, SLK_ABI_VERSION stays): numpy's
+ * RandomState.choice(num_items, size=count, p=p) over the ctx's MT19937 stream, bit for bit.  For the legacy RandomState that is
+ *     cdf = p.cumsum(); cdf /= cdf[-1]            (float64; formed by the HOST -- its contents are the host's responsibility,
+ *                                                  as ids are: non-decreasing, cdf[num_items - 1] == 1.0)
+ *     u   = random_sample(count)                  (per value TWO words a, b of the stream: ((a >> 5) * 2^26 + (b >> 6)) / 2^53)
+ *     idx = cdf.searchsorted(u, side='right')     (clamped to num_items - 1)
+ * No word is rejected: `count` values consume exactly 2 * count words -- also when num_items == 1 (slk_sample_items consumes
+ * nothing there, as randint does) --, T successive choice() calls are one draw of their total, and an item of weight zero is
+ * never returned (side='right' skips the flat stretches of the cdf, a leading one included).
+ *
+ * slk_cdf_guide fills the cutpoint table of a cdf: d_guide[b] = upper_bound(d_cdf, b / K) for b = 0 .. K, K = 2^guide_bits --
+ * K + 1 uint32 entries, exactly np.searchsorted(cdf, np.arange(K + 1) / K, 'right').  The CALLER owns d_guide (and d_cdf); the ctx
+ * retains neither, and a guide is valid for the cdf it was built from only.  guide_bits in [0, 28]; slk_cdf_guide_bits(num_items)
+ * is the automatic choice (the smallest K >= num_items, at most 2^24), so that a caller sizes the buffer by the library's rule.
+ * The guide only narrows the draw's binary search to [d_guide[bucket], d_guide[bucket + 1]], bucket = floor(u * K) (exact): the
+ * ids do not depend on guide_bits (0: one bucket, a plain binary search of the whole cdf).
+ *
+ * slk_sample_items_weighted writes `count` int64 ids to d_out and leaves (key, pos) where numpy's RandomState stands after the
+ * same choice() call.  It records the event slk_rng_get_state_sampled waits for, as slk_sample_items does.  count == 0 consumes
+ * nothing (d_out may then be NULL).  A count beyond option "weighted_max_values" is drawn as consecutive draws inside the call.
+ * Scratch: the ctx's generator buffers only; no host wait; both entries are profiled under SLK_K_SAMPLE.
+ * Refused with SLK_EINVAL: a NULL d_cdf / d_guide / d_out, num_items outside [1, 2^32], count < 0, guide_bits outside [0, 28]. */
+int32_t slk_cdf_guide_bits(int64_t num_items);
+int slk_cdf_guide(slk_ctx *ctx, const double *d_cdf, int64_t num_items, int32_t guide_bits, uint32_t *d_guide, void *stream);
+int slk_sample_items_weighted(slk_ctx *ctx, const double *d_cdf, const uint32_t *d_guide, int32_t guide_bits, int64_t num_items,
+                              int64_t count, int64_t *d_out, void *stream);
 
 /* The minibatch loop of one epoch of ImplicitFactorizationModel.fit() after the shuffle
  * (factorization/implicit.py:223-243): contiguous minibatches of `batch_size` over the n

@@ -65,6 +65,10 @@ _PROTOTYPES = {
     'slk_rng_get_state': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     'slk_rng_get_state_sampled': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     'slk_sample_items': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'slk_cdf_guide_bits': (C.c_int32, [C.c_int64]),
+    'slk_cdf_guide': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'slk_sample_items_weighted': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                            C.c_void_p]),
     'slk_bilinear_train': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p,
                                      C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -352,6 +356,20 @@ class Engine(object):
 
     def sample_items(self, num_items, count, d_out, stream=0):
         self._check(self._lib.slk_sample_items(self._ctx, int(num_items), int(count), d_out, stream))
+
+    def cdf_guide_bits(self, num_items):
+        """include/spotlight_hip.h: slk_cdf_guide_bits -- the automatic guide_bits of a cdf over num_items items."""
+        return int(self._lib.slk_cdf_guide_bits(int(num_items)))
+
+    def cdf_guide(self, d_cdf, num_items, guide_bits, d_guide, stream=0):
+        """d_guide[b] = upper_bound(d_cdf, b / 2^guide_bits), b = 0 .. 2^guide_bits (uint32; the caller's buffer)."""
+        self._check(self._lib.slk_cdf_guide(self._ctx, d_cdf, int(num_items), int(guide_bits), d_guide, stream))
+
+    def sample_items_weighted(self, d_cdf, d_guide, guide_bits, num_items, count, d_out, stream=0):
+        """RandomState.choice(num_items, size=count, p=p) over the ctx's stream: d_cdf = p.cumsum() / p.cumsum()[-1] in float64,
+        d_guide its cutpoint table (cdf_guide)."""
+        self._check(self._lib.slk_sample_items_weighted(self._ctx, d_cdf, d_guide, int(guide_bits), int(num_items), int(count),
+                                                        d_out, stream))
 
     # -- training / prediction ---------------------------------------------------------
     def bilinear_train(self, tables, optim, d_users, d_items, n, batch_size, loss, n_neg,

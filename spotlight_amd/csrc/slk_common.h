@@ -241,6 +241,9 @@ struct slk_ctx {
                                       // the same kind of switch
     int64_t opt_foldin_wg_min_len = 0;  // slk_bilinear_foldin: histories of at least this many interactions take the workgroup route (0: the
                                       // measured default, SLK_FOLDIN_WG_MIN_LEN in slk_foldin.hip); a test / measurement switch
+    int64_t opt_weighted_max_values = (int64_t)1 << 27;  // slk_sample_items_weighted: values per internal draw (2^27: 1 GiB of generated
+                                      // words); a larger count is a run of consecutive draws.  A test / measurement switch, the result
+                                      // does not depend on it
     int opt_user_bias_zero_hint = 1;  // 1: honour SLK_TABLES_USER_BIAS_ZERO (0: fetch the user biases regardless -- A/B and test switch)
     int64_t opt_record_nt_min_bytes = (int64_t)192 << 20;  // records of a minibatch from this size on are stored non-temporally
                                    // (slk_bilinear.hip::run_passes; 0: never)

@@ -11,6 +11,8 @@
 //   k_accept_count / k_scan_counts / k_accept_scatter   all CUs temper, test and compact;
 //   k_rng_finalize  restores (key, pos) to exactly what numpy would hold after the draw:
 //                   the state block containing the last CONSUMED word, pos = offset + 1.
+// The weighted draw, RandomState.choice(num_items, size, p=p), shares the generator and rejects nothing (further down:
+// k_cdf_guide / k_weighted_draw / k_rng_finalize_at).
 #include <math.h>
 #include <stddef.h>
 
@@ -511,6 +513,153 @@ int slk_sample_reserve(slk_ctx *ctx, int64_t num_items, int64_t count) {
     if (nblocks > (unsigned long long)slk_mt_jump_blocks(slk_mt_level_for(ctx, nblocks)) &&
         (rc = slk_mt_jump_reserve(ctx, slk_mt_level_for(ctx, nblocks))))
         return rc;
+    return SLK_OK;
+}
+
+// ---- the weighted draw: RandomState.choice(num_items, size, p=p) of the legacy RandomState, bit for bit -------------------
+//     cdf = p.cumsum(); cdf /= cdf[-1];  u = random_sample(size);  idx = cdf.searchsorted(u, side='right')
+// random_sample takes TWO words of the stream per value and rejects nothing, so value i reads the words pos + 2 i and
+// pos + 2 i + 1 (counted from block 0 = the ctx's key block) and the last consumed word is known before anything runs.
+//   k_cdf_guide      the cutpoint table: guide[b] = upper_bound(cdf, b / K), b = 0 .. K, K = 2^guide_bits.  u in bucket
+//                    b = floor(u K) has b / K <= u < (b + 1) / K, hence guide[b] <= upper_bound(cdf, u) <= guide[b + 1]
+//   k_weighted_draw  one value per thread: temper two words, u in double exactly as numpy forms it, the bucket (u K is exact:
+//                    K is a power of two), a binary search of the float64 cdf inside the bucket's range.  The guide only
+//                    narrows the search: the result is upper_bound's over the whole cdf, i.e. searchsorted's
+//   k_rng_finalize_at   (key, pos) behind a draw whose word count is known in closed form
+#define SLK_GUIDE_BITS_MAX 28
+#define SLK_GUIDE_BITS_AUTO_MAX 24  // slk_cdf_guide_bits: at most 2^24 + 1 cutpoints (64 MB)
+
+// first index in [lo, hi) whose cdf value is greater than x, hi if there is none
+__device__ __forceinline__ unsigned long long cdf_upper_bound(const double *cdf, unsigned long long lo, unsigned long long hi, double x) {
+    while (lo < hi) {
+        const unsigned long long mid = lo + ((hi - lo) >> 1);
+        if (cdf[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_cdf_guide(const double *cdf, unsigned long long num_items, unsigned long long K, uint32_t *guide) {
+    const unsigned long long b = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (b > K) return;
+    const unsigned long long g = cdf_upper_bound(cdf, 0, num_items, (double)b / (double)K);
+    guide[b] = g > 0xffffffffull ? 0xffffffffu : (uint32_t)g;  // (num_items == 2^32 only: the draw clamps to num_items - 1 anyway)
+}
+
+struct slk_wdraw_args {
+    const uint32_t *raw;
+    const slk_rng_dev *st;
+    const double *cdf;
+    const uint32_t *guide;
+    unsigned long long num_items, count;
+    double K;
+    int64_t *out;
+};
+
+__global__ __launch_bounds__(256) void k_weighted_draw(slk_wdraw_args a) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.count) return;
+    const unsigned long long w = (unsigned long long)a.st->pos + 2 * i;
+    // numpy's rk_double: (a >> 5, b >> 6) -> (a * 2^26 + b) / 2^53; every step is exact in double
+    const uint32_t hi27 = mt_temper(a.raw[w]) >> 5, lo26 = mt_temper(a.raw[w + 1]) >> 6;
+    const double u = ((double)hi27 * 67108864.0 + (double)lo26) / 9007199254740992.0;
+    const uint32_t bucket = (uint32_t)(u * a.K);
+    // (a guide that was not built from this cdf may make the result wrong, never the reads out of range)
+    unsigned long long hi = a.guide[bucket + 1], lo = a.guide[bucket];
+    if (hi > a.num_items) hi = a.num_items;
+    if (lo > hi) lo = hi;
+    unsigned long long idx = cdf_upper_bound(a.cdf, lo, hi, u);
+    if (idx > a.num_items - 1) idx = a.num_items - 1;
+    a.out[i] = (int64_t)idx;
+}
+
+// k_rng_finalize for a draw that consumed exactly `nwords` words from the current position: the state block that holds the
+// last of them becomes the key, pos = its offset + 1 (624 when it was the block's last word, as numpy leaves it)
+__global__ __launch_bounds__(256) void k_rng_finalize_at(slk_rng_dev *st, const uint32_t *raw, unsigned long long nwords) {
+    __shared__ unsigned long long s_tl;
+    if (threadIdx.x == 0) s_tl = (unsigned long long)st->pos + nwords - 1;
+    __syncthreads();
+    const unsigned long long tl = s_tl;
+    const unsigned long long blk = tl / SLK_MT_N;
+    for (int i = threadIdx.x; i < SLK_MT_N; i += 256) st->key[i] = raw[blk * SLK_MT_N + i];
+    __syncthreads();
+    if (threadIdx.x == 0) st->pos = (int32_t)(tl % SLK_MT_N) + 1;
+}
+
+SLK_EXPORT int32_t slk_cdf_guide_bits(int64_t num_items) {
+    int32_t bits = 0;
+    while (bits < SLK_GUIDE_BITS_AUTO_MAX && ((int64_t)1 << bits) < num_items) ++bits;
+    return bits;
+}
+
+static int weighted_check(slk_ctx *ctx, const char *who, const void *d_cdf, const void *d_guide, int64_t num_items, int32_t guide_bits) {
+    if (!d_cdf || !d_guide) return slk_fail(ctx, SLK_EINVAL, "%s: d_cdf or d_guide is NULL", who);
+    if (num_items < 1 || num_items > (int64_t)1 << 32)
+        return slk_fail(ctx, SLK_EINVAL, "%s: num_items %lld outside [1, 2^32]", who, (long long)num_items);
+    if (guide_bits < 0 || guide_bits > SLK_GUIDE_BITS_MAX)
+        return slk_fail(ctx, SLK_EINVAL, "%s: guide_bits %d outside [0, %d]", who, (int)guide_bits, SLK_GUIDE_BITS_MAX);
+    return SLK_OK;
+}
+
+SLK_EXPORT int slk_cdf_guide(slk_ctx *ctx, const double *d_cdf, int64_t num_items, int32_t guide_bits, uint32_t *d_guide, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int rc;
+    if ((rc = weighted_check(ctx, "slk_cdf_guide", d_cdf, d_guide, num_items, guide_bits))) return rc;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SAMPLE))) return rc;
+    const unsigned long long K = 1ull << guide_bits;
+    hipLaunchKernelGGL(k_cdf_guide, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, call.s, d_cdf, (unsigned long long)num_items, K,
+                       d_guide);
+    SLK_LAUNCH_CHECK(ctx, "k_cdf_guide");
+    return SLK_OK;
+}
+
+// one draw of `count` values (at most the generator's block limit): generate, draw, finalize
+static int weighted_draw(slk_ctx *ctx, const double *d_cdf, const uint32_t *d_guide, int32_t guide_bits, int64_t num_items,
+                         int64_t count, int64_t *d_out, hipStream_t s) {
+    const unsigned long long nwords = 2ull * (unsigned long long)count;
+    // the current key block may contribute nothing (pos == 624): 1 + ceil(nwords / 624) blocks hold pos + nwords words
+    const unsigned long long nblocks = 1ull + (nwords + SLK_MT_N - 1) / SLK_MT_N;
+    if (nblocks > 0x7fffffffull) return slk_fail(ctx, SLK_EINVAL, "slk_sample_items_weighted: count too large for one draw");
+    int rc;
+    if ((rc = slk_ensure(ctx, ctx->raw, nblocks * SLK_MT_N * 4))) return rc;
+    if ((rc = slk_mt_generate_blocks(ctx, nblocks, s))) return rc;
+    slk_wdraw_args a;
+    a.raw = (const uint32_t *)ctx->raw.p;
+    a.st = ctx->d_rng;
+    a.cdf = d_cdf;
+    a.guide = d_guide;
+    a.num_items = (unsigned long long)num_items;
+    a.count = (unsigned long long)count;
+    a.K = (double)(1ull << guide_bits);
+    a.out = d_out;
+    hipLaunchKernelGGL(k_weighted_draw, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, a);
+    SLK_LAUNCH_CHECK(ctx, "k_weighted_draw");
+    hipLaunchKernelGGL(k_rng_finalize_at, dim3(1), dim3(256), 0, s, ctx->d_rng, (const uint32_t *)ctx->raw.p, nwords);
+    SLK_LAUNCH_CHECK(ctx, "k_rng_finalize_at");
+    return SLK_OK;
+}
+
+SLK_EXPORT int slk_sample_items_weighted(slk_ctx *ctx, const double *d_cdf, const uint32_t *d_guide, int32_t guide_bits, int64_t num_items,
+                                         int64_t count, int64_t *d_out, void *stream) {
+    if (!ctx) return SLK_EINVAL;
+    int rc;
+    if ((rc = weighted_check(ctx, "slk_sample_items_weighted", d_cdf, d_guide, num_items, guide_bits))) return rc;
+    if (count < 0) return slk_fail(ctx, SLK_EINVAL, "slk_sample_items_weighted: negative count");
+    if (!d_out && count > 0) return slk_fail(ctx, SLK_EINVAL, "slk_sample_items_weighted: d_out is NULL");
+    if (count == 0) return SLK_OK;
+    slk_call call(ctx, stream);
+    if ((rc = call.begin(SLK_K_SAMPLE))) return rc;
+    // successive choice() calls are one contiguous draw, so a count beyond one draw's limit is a run of draws
+    for (int64_t done = 0; done < count;) {
+        const int64_t m = count - done < ctx->opt_weighted_max_values ? count - done : ctx->opt_weighted_max_values;
+        if ((rc = weighted_draw(ctx, d_cdf, d_guide, guide_bits, num_items, m, d_out + done, call.s))) return rc;
+        done += m;
+    }
+    // the stream position after this draw is final on the device once this event has fired (slk_rng_get_state_sampled)
+    if (!ctx->ev_sampled) SLK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_sampled, hipEventDisableTiming));
+    SLK_HIP(ctx, hipEventRecord(ctx->ev_sampled, call.s));
+    ctx->sampled_valid = true;
     return SLK_OK;
 }
 

@@ -16,6 +16,7 @@ from spotlight_amd.factorization._components import _predict_process_ids
 from spotlight_amd.factorization.representations import BilinearNet
 from spotlight_amd.helpers import _repr_model
 from spotlight_amd.layers import BloomEmbedding, ScaledEmbedding, ZeroEmbedding
+from spotlight_amd import sampling as _sampling
 from spotlight_amd.torch_utils import set_seed
 
 _ENGINES = {}
@@ -232,6 +233,7 @@ class _ImplicitEpochs(object):
 
     def __init__(self, model, binding, tables, n, device):
         self.binding, self.tables, self.n, self.device, self.num_items = binding, tables, n, device, model._num_items
+        self.dist = getattr(model, '_item_distribution', None)  # None: uniform negatives
         self.call = (n, model._batch_size, model._loss, model._num_negative_samples)
         self.mb_loss = torch.empty((n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
         self.slots, self.scopes, self.sources = [], [], None
@@ -252,8 +254,8 @@ class _ImplicitEpochs(object):
         d_users, d_items, d_neg = self.slots[epoch_num % 2]
         _epochs.device_epoch_shuffle(engine, random_state, self.n, self.d_perm,
                                      [(self.sources[0], d_users, 1), (self.sources[1], d_items, 1)], stream)
-        # one randint per minibatch == one contiguous draw over the epoch (sampling.py:34)
-        engine.sample_items(self.num_items, d_neg.numel(), d_neg.data_ptr(), stream=stream)
+        # one randint (one choice) per minibatch == one contiguous draw over the epoch (sampling.py:34)
+        _sampling.draw_items(engine, self.num_items, d_neg.numel(), d_neg.data_ptr(), stream, self.dist)
 
     def open_scopes(self, stack, engine, stream):
         shadow, pingpong = self.scopes
@@ -291,13 +293,24 @@ class ImplicitFactorizationModel(object):
       negatives exactly as the reference draws them, the embedding gathers and their backward through this package's
       kernels when the module is built from this package's layers.  Slower than the fused path by the reference's own
       per-minibatch overheads, never on the CPU.
+    * `negative_sampling` (not in the reference): what the negatives are drawn from.  'uniform' or None: every item alike
+      (`RandomState.randint`, the reference's sampler).  'popularity': in proportion to
+      `count(item) ** negative_sampling_power` (word2vec's unigram distribution; default power 0.75), the counts taken over
+      the interactions of the fit() call in progress -- an item that does not occur there has weight 0 and is NEVER drawn as
+      a negative.  An array of `num_items` finite, non-negative weights with a positive sum: in proportion to them (checked
+      at fit(); ValueError before anything is drawn).  A weighted draw is `RandomState.choice(num_items, size=..., p=p)` on
+      the model's RandomState, made on the device bit for bit (csrc/slk_rng.hip); fit() then prepares every epoch's
+      negatives beside the epoch before it at every size (the two-lane schedule), and fold_in() draws from the distribution
+      of the last fit().
     """
 
     def __init__(self, loss='pointwise', embedding_dim=32, n_iter=10, batch_size=256, l2=0.0,
                  learning_rate=1e-2, optimizer_func=None, use_cuda=False, representation=None,
-                 sparse=False, random_state=None, num_negative_samples=5):
+                 sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
+                 negative_sampling_power=0.75):
 
         assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge')
+        _sampling.check_negative_sampling(negative_sampling)
 
         self._loss = loss
         self._embedding_dim = embedding_dim
@@ -311,6 +324,9 @@ class ImplicitFactorizationModel(object):
         self._optimizer_func = optimizer_func
         self._random_state = random_state or np.random.RandomState()
         self._num_negative_samples = num_negative_samples
+        self._negative_sampling = negative_sampling
+        self._negative_sampling_power = negative_sampling_power
+        self._item_distribution = None  # sampling.ItemDistribution of the last fit() (None: uniform)
 
         self._num_users = None
         self._num_items = None
@@ -418,7 +434,10 @@ class ImplicitFactorizationModel(object):
         n = len(user_ids)
         nn = self._num_negative_samples if self._loss == 'adaptive_hinge' else 1
         autograd = getattr(self, '_autograd_route', False)
-        small = self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS
+        # non-uniform negatives are handed in at every size (the two-lane schedule): the three-stage pipeline's
+        # slk_bilinear_prefetch draws uniform ones ahead of time
+        weighted = not _sampling.is_uniform(getattr(self, '_negative_sampling', None))
+        small = weighted or (self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS)
         # the id-range checks (implicit.py:169-182): four reductions over the host arrays, 12 ms at 2^25 ids.  On the large-epoch
         # path they run on worker threads beside the id upload and the first epoch's shuffle; their verdict is collected before
         # the first training call is enqueued (nothing the caller can observe has changed by then: the RandomState is restored,
@@ -427,6 +446,10 @@ class ImplicitFactorizationModel(object):
                                   threaded=not (autograd or small) and n >= _DEFERRED_CHECK_MIN)
         if not check.threaded:
             check.result()
+        # the item weights of this fit(): validated (ValueError) before anything is drawn from the RandomState
+        self._item_distribution = _sampling.item_distribution(getattr(self, '_negative_sampling', None),
+                                                              getattr(self, '_negative_sampling_power', 0.75), self._num_items,
+                                                              item_ids)
         if autograd:
             return self._fit_autograd(user_ids, item_ids, verbose)
         binding = self._bind()
@@ -434,6 +457,8 @@ class ImplicitFactorizationModel(object):
         engine = _engine_for(device)
         stream = _stream_for(device)
         tables = self._slk_tables()
+        if self._item_distribution is not None:
+            self._item_distribution.bind(engine, device, stream)
         # bpr / hinge leave the user biases' gradient at exactly zero (+g - g), so a model the reference initialised (ZeroEmbedding)
         # keeps them identically zero; checked HERE, on the device, once per fit(): the user pass then does not fetch a cache line
         # per interaction for a table of zeros (include/spotlight_hip.h: SLK_TABLES_USER_BIAS_ZERO).  Same values either way.
@@ -475,7 +500,8 @@ class ImplicitFactorizationModel(object):
         self._net.train(True)
 
         def negatives_for(batch_user, n_draws):
-            return torch.from_numpy(sample_items(self._num_items, n_draws, random_state=self._random_state)).to(device)
+            return torch.from_numpy(sample_items(self._num_items, n_draws, random_state=self._random_state,
+                                                 p=self._item_distribution)).to(device)
 
         for epoch_num in range(self._n_iter):
             users, items = shuffle(user_ids, item_ids, random_state=self._random_state)

@@ -345,6 +345,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         super(ShardedImplicitFactorizationModel, self).__init__(*args, **kwargs)
         if self._representation is not None:
             raise NotImplementedError('custom representations are not supported by the row-sharded path')
+        if self._negative_sampling is not None and not (isinstance(self._negative_sampling, str) and self._negative_sampling == 'uniform'):
+            raise NotImplementedError('the row-sharded path draws uniform negatives: negative_sampling is not supported')
         self._trainer = None
 
     def __getstate__(self):

@@ -18,6 +18,7 @@ import torch.optim as optim
 
 from spotlight_amd import _native
 from spotlight_amd import recommend as _rec
+from spotlight_amd import sampling as _sampling
 from spotlight_amd.factorization import implicit as _host
 from spotlight_amd.layers import BloomEmbedding
 
@@ -78,7 +79,8 @@ def _fresh_optimizer(model, params):
 
 def _negatives(model, negatives, T, nn, n, device, engine, stream):
     """int64 device tensor [T, nn, n]: the caller's, or drawn on the device from the model's RandomState exactly as T successive
-    sample_items(num_items, (nn, n)) calls would draw them (one contiguous draw: state set, draw, state read back, as fit())."""
+    sample_items(num_items, (nn, n)) calls would draw them (one contiguous draw: state set, draw, state read back, as fit()) -- with
+    the item weights of the model's last fit() (`negative_sampling`) as T successive choice(num_items, (nn, n), p=p) calls would."""
     if negatives is not None:
         neg = np.ascontiguousarray(np.asarray(negatives), dtype=np.int64)
         if neg.shape == (T, n) and nn == 1:
@@ -91,8 +93,11 @@ def _negatives(model, negatives, T, nn, n, device, engine, stream):
         return torch.from_numpy(neg).to(device)
     out = torch.empty((T, nn, max(n, 1)) if n == 0 else (T, nn, n), dtype=torch.int64, device=device)
     if n:
+        dist = getattr(model, '_item_distribution', None)  # the item weights of the last fit() (None: uniform)
+        if dist is not None:
+            dist.bind(engine, device, stream)
         engine.rng_set_state(model._random_state.get_state())
-        engine.sample_items(model._num_items, T * nn * n, out.data_ptr(), stream)
+        _sampling.draw_items(engine, model._num_items, T * nn * n, out.data_ptr(), stream, dist)
         model._random_state.set_state(engine.rng_get_state())
     return out
 

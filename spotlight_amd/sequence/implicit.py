@@ -14,6 +14,7 @@ import torch
 import torch.optim as optim
 
 from spotlight_amd import _epochs, _native
+from spotlight_amd import sampling as _sampling
 from spotlight_amd.factorization import implicit as _host
 from spotlight_amd.factorization.implicit import _OptimizerBinding
 from spotlight_amd.helpers import _repr_model
@@ -65,7 +66,8 @@ class _SequenceEpochs(object):
         _epochs.device_epoch_shuffle(engine, random_state, self.n_seq, self.d_perm,
                                      [(self.bufs[epoch_num % 2], self.bufs[(epoch_num + 1) % 2], self.seq_len)], stream)
         if self.draws:
-            engine.sample_items(self.model._num_items, self.draws, self.negs[epoch_num % 2].data_ptr(), stream=stream)
+            _sampling.draw_items(engine, self.model._num_items, self.draws, self.negs[epoch_num % 2].data_ptr(), stream,
+                                 self.model._item_distribution)
 
     def train(self, engine, stream, epoch_num):
         ostruct = self.binding.as_struct()
@@ -83,13 +85,23 @@ class ImplicitSequenceModel(object):
     'cnn' / 'lstm' / 'mixture' / a module with user_representation + forward (encoder body on
     torch autograd, embedding lookups and their backward on this package's kernels).  `use_cuda`
     is accepted for signature compatibility; the model always lives on the HIP device.
+
+    `negative_sampling` (not in the reference): 'uniform' or None draws every negative with `RandomState.randint`, as the
+    reference does.  'popularity' draws in proportion to `count(item) ** negative_sampling_power` (default 0.75), the counts
+    taken over the `sequences` of the fit() call in progress with the padding item 0 given weight 0: neither the padding item
+    nor an item that does not occur there is ever a negative.  An array of `num_items` finite, non-negative weights with a
+    positive sum: in proportion to them, as given (checked at fit(); ValueError before anything is drawn).  A weighted draw
+    is `RandomState.choice(num_items, size=shape, p=p)` on the model's RandomState, made on the device bit for bit; the fused
+    (PoolNet) fit() then prepares every epoch's negatives beside the epoch before it at every size.
     """
 
     def __init__(self, loss='pointwise', representation='pooling', embedding_dim=32, n_iter=10,
                  batch_size=256, l2=0.0, learning_rate=1e-2, optimizer_func=None, use_cuda=False,
-                 sparse=False, random_state=None, num_negative_samples=5):
+                 sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
+                 negative_sampling_power=0.75):
 
         assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge')
+        _sampling.check_negative_sampling(negative_sampling)
 
         if isinstance(representation, str):
             assert representation in ('pooling', 'cnn', 'lstm', 'mixture')
@@ -106,6 +118,9 @@ class ImplicitSequenceModel(object):
         self._optimizer_func = optimizer_func
         self._random_state = random_state or np.random.RandomState()
         self._num_negative_samples = num_negative_samples
+        self._negative_sampling = negative_sampling
+        self._negative_sampling_power = negative_sampling_power
+        self._item_distribution = None  # sampling.ItemDistribution of the last fit() (None: uniform)
 
         self._num_items = None
         self._net = None
@@ -195,6 +210,10 @@ class ImplicitSequenceModel(object):
             self._initialize(interactions)
 
         self._check_input(sequences)
+        # the item weights of this fit(): validated (ValueError) before anything is drawn from the RandomState
+        self._item_distribution = _sampling.item_distribution(getattr(self, '_negative_sampling', None),
+                                                              getattr(self, '_negative_sampling_power', 0.75), self._num_items,
+                                                              sequences, zero=(PADDING_IDX,))
 
         if not isinstance(self._net, PoolNet):
             return self._fit_autograd(sequences, verbose)
@@ -204,7 +223,10 @@ class ImplicitSequenceModel(object):
         engine = _host._engine_for(device)
         stream = _host._stream_for(device)
         nn = self._num_negative_samples if self._loss == 'adaptive_hinge' else 1
-        ahead = self._n_iter > 1 and sequences.size * nn <= _host._PIPELINE_MAX_DRAWS
+        if self._item_distribution is not None:
+            self._item_distribution.bind(engine, device, stream)
+        # (non-uniform negatives are handed in at every size: slk_poolnet_train draws uniform ones itself)
+        ahead = self._item_distribution is not None or (self._n_iter > 1 and sequences.size * nn <= _host._PIPELINE_MAX_DRAWS)
         job = _SequenceEpochs(self, binding, self._slk_tables(), sequences.shape, nn if ahead else 0, device)
         job.reserve(engine, stream)
         job.upload(sequences)
@@ -232,6 +254,8 @@ class ImplicitSequenceModel(object):
         n_neg = self._num_negative_samples if self._loss == 'adaptive_hinge' else 1
         d_negatives = torch.empty(n_neg * self._batch_size * seq_len, dtype=torch.int64, device=device)
         self._net.train(True)
+        if self._item_distribution is not None:
+            self._item_distribution.bind(engine, device, stream)
         for epoch_num in range(self._n_iter):
             engine.rng_set_state(self._random_state.get_state())
             _host.device_epoch_shuffle(engine, self._random_state, n_seq, d_perm, [(d_prev, d_sequences, seq_len)],
@@ -243,7 +267,7 @@ class ImplicitSequenceModel(object):
                 representation, _ = self._net.user_representation(batch)
                 positive = self._net(representation, batch)
                 count = n_neg * rows * seq_len
-                engine.sample_items(self._num_items, count, d_negatives.data_ptr(), stream=stream)
+                _sampling.draw_items(engine, self._num_items, count, d_negatives.data_ptr(), stream, self._item_distribution)
                 negative_items = d_negatives[:count].view(n_neg * rows, seq_len)
                 if self._loss == 'adaptive_hinge':
                     tiled = representation.repeat(*((n_neg,) + (1,) * (representation.dim() - 1)))
