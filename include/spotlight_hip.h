@@ -309,6 +309,33 @@ int slk_bilinear_train_explicit(slk_ctx *ctx, const slk_tables *tables, slk_opti
                                 const int64_t *d_users, const int64_t *d_items, const float *d_ratings,
                                 int64_t n, int64_t batch_size, int32_t loss, float *d_mb_loss, void *stream);
 
+/* Interaction weights (added to ABI 14: one new entry, nothing existing changes, SLK_ABI_VERSION stays): slk_bilinear_train
+ * (d_ratings NULL) or slk_bilinear_train_explicit (d_ratings given; n_neg, d_neg_in, d_neg_out are then ignored) with a weight
+ * per interaction.  For a minibatch with per-interaction losses l_i and weights w_i = d_weights[i]
+ *     L = sum_i(w_i * l_i) / sum_i(w_i)
+ * l_i the per-interaction term of the unweighted loss (pointwise: (1 - sigmoid(p)) + sigmoid(n); bpr: 1 - sigmoid(p - n);
+ * hinge: max(0, n - p + 1); regression / poisson / logistic as in slk_bilinear_train_explicit).  Adaptive hinge: column c of
+ * the reference's view(n, B) layout carries the weight of ITS positive (interaction k0 + c) on the positive and on the selected
+ * negative alike, whichever interaction's row that negative was drawn in.  d_mb_loss[m] = L of minibatch m.  Ids, negatives
+ * and the ctx's RNG stream are exactly those of the unweighted call.
+ *   The sum W = sum(w_i) of a minibatch is formed in float64 in an order that depends on the minibatch's length alone (not on
+ * the grid, the occupancy or the call's chunks), rounded ONCE to fp32, inv_W = 1.0f / (float)W; dL/dscore is the unweighted
+ * factor without its 1 / B, times w_i, times inv_W, in that order.  Hence all-ones weights give the unweighted staged call's
+ * tables bit for bit, and a power of two on every weight changes nothing, bit for bit.  (Poisson / logistic keep the shape
+ * of their unweighted dL/dscore, with w_i * inv_W for 1 / B and a division by (float)W for the division by B.)
+ *   d_weights is NOT checked here (as ids are not): finite and > 0 is the caller's responsibility -- an interaction of weight 0
+ * is one to drop, a minibatch whose weights sum to 0 has no loss (spotlight_amd validates at fit()).
+ *   Every loss takes the staged route (scores, a loss kernel, the user pass reading dL/dscore): options "epoch_kernel" and
+ * "explicit_fused" do not apply.  Inside an item-bias shadow scope the call trains as adaptive hinge does; inside a user-row
+ * ping-pong scope it is refused (SLK_EINVAL; the scope stays usable).  A chunk prepared ahead by slk_bilinear_prefetch is
+ * dropped, as by a call that draws nothing.  slk_bilinear_reserve of the same shape covers the weight sums' scratch; the
+ * staged route's own buffers grow on the first call.  Refused with SLK_EINVAL: d_weights NULL with n > 0; ratings with a
+ * loss that is not regression / poisson / logistic (and the reverse). */
+int slk_bilinear_train_weighted(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_users,
+                                const int64_t *d_items, const float *d_weights, const float *d_ratings, int64_t n,
+                                int64_t batch_size, int32_t loss, int32_t n_neg, const int64_t *d_neg_in, int64_t *d_neg_out,
+                                float *d_mb_loss, void *stream);
+
 /* The FIRST chunk of the next slk_bilinear_train call with these very arguments, prepared NOW (ABI 7): its negatives and
  * sorts -- and the negatives of the call's OTHER chunks too, when the call draws fewer than 2^30 of them: one contiguous draw,
  * after which slk_rng_get_state_sampled returns the stream position behind the whole call -- run on the ctx's second stream

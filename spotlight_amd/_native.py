@@ -74,6 +74,9 @@ _PROTOTYPES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_bilinear_train_explicit': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'slk_bilinear_train_weighted': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_bilinear_prefetch': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     'slk_bilinear_reserve': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_int64, C.c_int64,
@@ -384,6 +387,15 @@ class Engine(object):
         self._check(self._lib.slk_bilinear_train_explicit(
             self._ctx, C.byref(tables), C.byref(optim), d_users, d_items, d_ratings, int(n), int(batch_size),
             LOSS_KINDS[loss] if isinstance(loss, str) else int(loss), d_mb_loss, stream))
+
+    def bilinear_train_weighted(self, tables, optim, d_users, d_items, d_weights, n, batch_size, loss, n_neg, d_mb_loss,
+                                d_ratings=None, d_neg_in=None, d_neg_out=None, stream=0):
+        """include/spotlight_hip.h: slk_bilinear_train_weighted -- bilinear_train (d_ratings None) or bilinear_train_explicit
+        with float32 interaction weights d_weights[n]: per minibatch L = sum(w * l) / sum(w).  The weights' values are the
+        caller's responsibility (finite, > 0)."""
+        self._check(self._lib.slk_bilinear_train_weighted(
+            self._ctx, C.byref(tables), C.byref(optim), d_users, d_items, d_weights, d_ratings, int(n), int(batch_size),
+            LOSS_KINDS[loss] if isinstance(loss, str) else int(loss), int(n_neg), d_neg_in, d_neg_out, d_mb_loss, stream))
 
     def bilinear_prefetch(self, tables, optim, d_users, d_items, n, batch_size, loss, n_neg, state=None, stream=0):
         """Prepares the first chunk of the next bilinear_train call with these arguments on the ctx's second stream; `state`: the

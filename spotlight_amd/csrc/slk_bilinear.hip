@@ -650,6 +650,78 @@ __global__ __launch_bounds__(256) void k_explicit_loss(const float *sk, const fl
 }
 
 // ---------------------------------------------------------------------------------------
+// interaction weights (slk_bilinear_train_weighted): L = sum(w_i l_i) / sum(w_i) per minibatch
+// ---------------------------------------------------------------------------------------
+// W_m = sum of the weights of minibatch m, in float64, in an order fixed by the minibatch's length alone: segment j of the
+// minibatch (SLK_WSEG consecutive weights) is summed by ONE workgroup -- thread t adds elements t, t + 256, ... of the segment
+// in turn, then the block tree (slk_block_sum_256) -- and the segments' sums are added the same way by one workgroup per
+// minibatch.  Which workgroup takes which segment, the grid and the chunk the minibatch falls in do not enter.
+#define SLK_WSEG 8192u
+__global__ __launch_bounds__(256) void k_weight_partials(const float *w, uint32_t nc, uint32_t per_mb, uint32_t segs_per_mb,
+                                                         double *wpart) {
+    __shared__ double red[256];
+    const uint32_t n_mb = (nc + per_mb - 1) / per_mb;
+    for (uint32_t i = blockIdx.x; i < n_mb * segs_per_mb; i += gridDim.x) {
+        const uint32_t mb = i / segs_per_mb, seg = i - mb * segs_per_mb;
+        const uint32_t w0 = mb * per_mb, w1 = (nc - w0 < per_mb) ? nc : w0 + per_mb;
+        // (a short last minibatch has empty segments: they are written as 0.0 and add nothing)
+        const uint32_t s0 = (w1 - w0 > seg * SLK_WSEG) ? w0 + seg * SLK_WSEG : w1, s1 = (w1 - s0 < SLK_WSEG) ? w1 : s0 + SLK_WSEG;
+        double x = 0.0;
+        for (uint32_t e = s0 + threadIdx.x; e < s1; e += 256) x += (double)w[e];
+        const double tot = slk_block_sum_256(x, red);
+        if (threadIdx.x == 0) wpart[i] = tot;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_weight_sums(const double *wpart, uint32_t n_mb, uint32_t segs_per_mb, double *wsum) {
+    __shared__ double red[256];
+    for (uint32_t mb = blockIdx.x; mb < n_mb; mb += gridDim.x) {
+        double x = 0.0;
+        for (uint32_t j = threadIdx.x; j < segs_per_mb; j += 256) x += wpart[(size_t)mb * segs_per_mb + j];
+        const double tot = slk_block_sum_256(x, red);
+        if (threadIdx.x == 0) wsum[mb] = tot;
+    }
+}
+
+// The pair losses (pointwise, bpr, hinge) behind k_score_pass with NP == 2: one thread per interaction of the minibatch, in
+// the shape of k_explicit_loss.  sk / gk / w are chunk-local (k0 = the minibatch's first interaction); *wsum = W of this
+// minibatch.  The loss partials leave already divided by W: the item pass's finalisation runs with inv_b = 1.
+__global__ __launch_bounds__(256) void k_pair_loss_weighted(const float *sk, const float *w, float *gk, uint32_t k0, uint32_t bm,
+                                                            int loss_kind, const double *wsum, double *loss_partial) {
+    __shared__ double red[256];
+    const float inv_W = 1.0f / (float)*wsum;
+    double lsum = 0.0;
+    for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < bm; c += gridDim.x * 256) {
+        const size_t at = 2 * (size_t)(k0 + c);
+        const float wc = w[k0 + c];
+        float l, gp, gn;
+        slk_pair_loss(loss_kind, sk[at], sk[at + 1], 1.0f, l, gp, gn);  // (x * 1.0f is x: the factors without their 1 / B)
+        gk[at] = slk_weight_scale(gp, wc, inv_W);
+        gk[at + 1] = slk_weight_scale(gn, wc, inv_W);
+        lsum += (double)wc * (double)l;
+    }
+    const double tot = slk_block_sum_256(lsum, red);
+    if (threadIdx.x == 0) loss_partial[blockIdx.x] = tot * (double)inv_W;
+}
+
+__global__ __launch_bounds__(256) void k_explicit_loss_weighted(const float *sk, const float *ratings, const float *w, float *gk,
+                                                                uint32_t k0, uint32_t bm, int loss_kind, const double *wsum,
+                                                                double *loss_partial) {
+    __shared__ double red[256];
+    const float Wf = (float)*wsum, inv_W = 1.0f / Wf;
+    double lsum = 0.0;
+    for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < bm; c += gridDim.x * 256) {
+        const float wc = w[k0 + c];
+        float l, g;
+        slk_explicit_loss_weighted(loss_kind, sk[k0 + c], ratings[k0 + c], wc, inv_W, Wf, l, g);
+        gk[k0 + c] = g;
+        lsum += (double)wc * (double)l;
+    }
+    const double tot = slk_block_sum_256(lsum, red);
+    if (threadIdx.x == 0) loss_partial[blockIdx.x] = tot * (double)inv_W;
+}
+
+// ---------------------------------------------------------------------------------------
 // dense sweeps (reference default optimizer: Adam with weight_decay = l2 over EVERY row)
 // ---------------------------------------------------------------------------------------
 
@@ -1033,7 +1105,7 @@ SLK_EXPORT int slk_bilinear_predict(slk_ctx *ctx, const slk_tables *tables, cons
 // and its minibatches (run_chunk: score_stage, user_stage, item_stage) in line (run_inline), one chunk ahead
 // (run_pipelined), or the first chunk a whole call ahead (prefetch_first_chunk).
 // ---------------------------------------------------------------------------------------------------------------------------
-struct train_call {  // the arguments as given (ratings: explicit feedback, and only it)
+struct train_call {  // the arguments as given (ratings: explicit feedback, and only it; weights: slk_bilinear_train_weighted, and only it)
     enum { TRAIN, RESERVE, PREFETCH } mode;
     const slk_tables *tables;
     slk_optim *optim;
@@ -1045,6 +1117,7 @@ struct train_call {  // the arguments as given (ratings: explicit feedback, and 
     int64_t n, batch_size;
     int32_t loss, n_neg;
     hipStream_t s;
+    const float *weights;
 };
 
 struct train_plan {  // everything derived from a call and the ctx's options before any GPU work
@@ -1057,8 +1130,9 @@ struct train_plan {  // everything derived from a call and the ctx's options bef
     slk_bloom_dev ubd, ibd;  // BloomEmbedding layers (layers.py:74-244): keys of the row-owner passes are hashed rows
     int Hu, Hi;
     // expl: explicit feedback (ratings, no negatives); fused: ... whose user pass forms score, loss and dL/dscore itself (option
-    // "explicit_fused"); pre: dL/dscore is computed before the user pass
-    bool bloom, adaptive, expl, fused, pre, dense, late;
+    // "explicit_fused"); pre: dL/dscore is computed before the user pass; weighted: interaction weights -- every loss staged
+    // (`pre`, never `fused`, never the persistent route), the pair losses with their NP = 2 through k_pair_loss_weighted
+    bool bloom, adaptive, expl, fused, pre, dense, late, weighted;
     int nn, NP, umode, nsets;
     int64_t bsz, mb_per_chunk, chunk_cap, occ_mult;
     // chunk ck is [ck * chunk_cap, min(n, (ck + 1) * chunk_cap)): nc_max interactions in the largest (= the first); 0 chunks: an empty call
@@ -1089,6 +1163,8 @@ static inline uint32_t chunk_len(const train_plan &p, const train_call &c, size_
     const int64_t c1 = chunk_begin(p, ck + 1);
     return (uint32_t)((c1 < c.n ? c1 : c.n) - chunk_begin(p, ck));
 }
+
+static inline uint32_t weight_segs(const train_plan &p) { return (uint32_t)(((size_t)p.bsz + SLK_WSEG - 1) / SLK_WSEG); }
 
 static int run_training(slk_ctx *ctx, const train_call &c);
 
@@ -1144,6 +1220,20 @@ SLK_EXPORT int slk_bilinear_train_explicit(slk_ctx *ctx, const slk_tables *table
                               batch_size, loss, 0, (hipStream_t)stream});
 }
 
+// Interaction weights (include/spotlight_hip.h): either loss family with L = sum(w_i l_i) / sum(w_i) per minibatch.  Every
+// loss takes the staged route -- k_score_pass, a weighted loss kernel, the user pass reading dL/dscore (UMODE 1) -- so that
+// neither hot pass knows of the weights.  The weights' VALUES are the caller's responsibility, as ids are.
+SLK_EXPORT int slk_bilinear_train_weighted(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_users,
+                                           const int64_t *d_items, const float *d_weights, const float *d_ratings, int64_t n,
+                                           int64_t batch_size, int32_t loss, int32_t n_neg, const int64_t *d_neg_in,
+                                           int64_t *d_neg_out, float *d_mb_loss, void *stream) {
+    if (ctx && n > 0 && !d_weights) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_weighted: d_weights is NULL");
+    // (n == 0: a no-op like every training call; a non-NULL stand-in keeps the plan a weighted one, so the refusals are the same)
+    static const float none = 1.0f;
+    return run_training(ctx, {train_call::TRAIN, tables, optim, d_users, d_items, d_ratings, d_neg_in, d_neg_out, d_mb_loss, n,
+                              batch_size, loss, d_ratings ? 0 : n_neg, (hipStream_t)stream, d_weights ? d_weights : &none});
+}
+
 // Every derived value of a call and every refusal, in the order the rules have always been checked in (where a call breaks
 // several, the first one answers).  Touches nothing on the GPU; of the ctx only the current device and the noted stream.
 static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
@@ -1164,8 +1254,9 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
     p.expl = c.loss >= SLK_LOSS_REGRESSION;
     if (p.expl != (c.ratings != nullptr) && !reserve)
         return slk_fail(ctx, SLK_EINVAL, "ratings go with (and only with) the regression/poisson/logistic losses");
-    p.fused = p.expl && ctx->opt_explicit_fused;
-    p.pre = p.adaptive || p.expl;
+    p.weighted = c.weights != nullptr;
+    p.fused = p.expl && ctx->opt_explicit_fused && !p.weighted;
+    p.pre = p.adaptive || p.expl || p.weighted;
     p.umode = p.fused ? 2 : (p.pre ? 1 : 0);
     p.nn = p.adaptive ? c.n_neg : (p.expl ? 0 : 1);
     if (!p.expl && (p.nn < 1 || p.nn > 1024)) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", p.nn);
@@ -1206,7 +1297,7 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
         return slk_fail(ctx, SLK_EINVAL, "batch_size * lookups per interaction must be < 2^31");
     // the persistent route (slk_epoch.hip) keeps per-(minibatch, workgroup) loss partials and counts barriers in 32 bits:
     // at most 2^13 minibatches per launch (16 MB of partials at 256 workgroups)
-    const bool maybe_epoch = ctx->opt_epoch_kernel && !ctx->epoch_refused && bsz <= ctx->opt_epoch_max_batch;
+    const bool maybe_epoch = ctx->opt_epoch_kernel && !ctx->epoch_refused && bsz <= ctx->opt_epoch_max_batch && !p.weighted;
     if (maybe_epoch && mb_per_chunk > ((int64_t)1 << 13)) mb_per_chunk = (int64_t)1 << 13;
     p.mb_per_chunk = mb_per_chunk;
     // chunks of chunk_cap.  Chunking is value-neutral: the negatives of a call are one contiguous draw however
@@ -1246,6 +1337,9 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
     if (ctx->pp_active && !p.pingpong && !reserve)
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: a user-row ping-pong (slk_user_pingpong_begin) is open on this ctx for OTHER "
                                          "tables; close it (slk_user_pingpong_end / _abort) before training another model");
+    if (p.pingpong && p.weighted)
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_weighted: the user rows are ping-ponged (slk_user_pingpong_begin): a call "
+                                         "with interaction weights forms dL/dscore ahead of the user pass and does not train inside the scope");
     if (p.pingpong && (p.pre || p.bloom || p.dense || tables->num_users != ctx->pp_rows || p.D != ctx->pp_dim))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: the user rows are ping-ponged (slk_user_pingpong_begin): only the pair losses "
                                          "(pointwise, bpr, hinge) over plain tables of the scope's shape with a row-sparse optimizer train inside the scope");
@@ -1268,7 +1362,7 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: an item-bias shadow (slk_bias_shadow_begin) is open on this ctx for OTHER "
                                          "tables; close it (slk_bias_shadow_end / _abort) before training another model");
     // minibatches of a few thousand interactions: every minibatch of a chunk inside ONE persistent launch (slk_epoch.hip)
-    p.epoch_route = !p.shadowed && !p.pingpong && (!p.pre || p.adaptive || p.fused) &&
+    p.epoch_route = !p.weighted && !p.shadowed && !p.pingpong && (!p.pre || p.adaptive || p.fused) &&
                     slk_epoch_eligible(ctx, tables, optim, bsz, c.loss, p.bloom);
     p.dense_elems[0] = (size_t)(Hu ? p.ubd.rows : tables->num_users) * p.D;
     p.dense_elems[1] = (size_t)(Hi ? p.ibd.rows : tables->num_items) * p.D;
@@ -1316,6 +1410,13 @@ static int ensure_scratch(slk_ctx *ctx, const train_plan &p, hipStream_t s) {
     if (p.pre) {
         if ((rc = slk_ensure(ctx, ctx->gk, nc_max * NP * 4))) return rc;
         if ((rc = slk_ensure(ctx, ctx->sk, nc_max * NP * 4))) return rc;
+    }
+    // the weight sums of a chunk's minibatches and their per-segment partials (k_weight_partials): a few KB, so a plan of
+    // ANY kind holds them -- slk_bilinear_reserve does not know whether the call it stands for carries weights
+    {
+        const size_t n_mb = (nc_max + bsz - 1) / bsz;
+        if ((rc = slk_ensure(ctx, ctx->extra[BL_WSUM], n_mb * 8))) return rc;
+        if ((rc = slk_ensure(ctx, ctx->extra[BL_WPART], n_mb * weight_segs(p) * 8))) return rc;
     }
     if (late) {
         // (the live lists are sorted per minibatch on the PASSES' stream; with the overlapped prep another chunk's sorts run on
@@ -1642,14 +1743,26 @@ static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, c
     hipLaunchKernelGGL(k.spass, dim3(mb.ugrid), dim3(256), 0, s, a);
     SLK_LAUNCH_CHECK(ctx, "k_score_pass");
     const unsigned sgrid = slk_grid_for(ctx, mb.bm, 256);
-    if (p.expl) {
+    // interaction weights: chunk-local as the ratings are; this minibatch's W in the chunk's sums (weight_sums)
+    const float *const wts = p.weighted ? c.weights + chunk_begin(p, ck) : nullptr;
+    const double *const wsum = p.weighted ? (const double *)ctx->extra[BL_WSUM].p + mb.b0 / (uint32_t)p.bsz : nullptr;
+    if (p.weighted && p.expl) {
+        hipLaunchKernelGGL(k_explicit_loss_weighted, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p,
+                           c.ratings + chunk_begin(p, ck), wts, f32p(ctx->gk), mb.b0, mb.bm, (int)c.loss, wsum,
+                           (double *)ctx->losspart.p);
+        SLK_LAUNCH_CHECK(ctx, "k_explicit_loss_weighted");
+    } else if (p.weighted && !p.adaptive) {
+        hipLaunchKernelGGL(k_pair_loss_weighted, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, wts, f32p(ctx->gk), mb.b0,
+                           mb.bm, (int)c.loss, wsum, (double *)ctx->losspart.p);
+        SLK_LAUNCH_CHECK(ctx, "k_pair_loss_weighted");
+    } else if (p.expl) {
         hipLaunchKernelGGL(k_explicit_loss, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, c.ratings + chunk_begin(p, ck),
                            f32p(ctx->gk), mb.b0, mb.bm, (int)c.loss, a.inv_b, (double *)ctx->losspart.p);
         SLK_LAUNCH_CHECK(ctx, "k_explicit_loss");
     } else {
         hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, f32p(ctx->gk), mb.b0, mb.bm,
                            p.nn, a.inv_b, (double *)ctx->losspart.p, p.late ? (const uint32_t *)pb.ipay[0].p : (const uint32_t *)nullptr,
-                           p.late ? u32p(ctx->extra[BL_LIVE]) : (uint32_t *)nullptr);
+                           p.late ? u32p(ctx->extra[BL_LIVE]) : (uint32_t *)nullptr, wts, wsum);
         SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
     }
     a.n_loss_partial = (int)sgrid;
@@ -1772,6 +1885,21 @@ static int item_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, co
     return SLK_OK;
 }
 
+// W_m of every minibatch of chunk `ck` (BL_WSUM), once per chunk, on the passes' stream ahead of the chunk's first score stage
+static int weight_sums(slk_ctx *ctx, const train_plan &p, const train_call &c, size_t ck, hipStream_t s) {
+    const uint32_t nc = chunk_len(p, c, ck), bsz = (uint32_t)p.bsz, n_mb = (nc + bsz - 1) / bsz, segs = weight_segs(p);
+    double *const wpart = (double *)ctx->extra[BL_WPART].p, *const wsum = (double *)ctx->extra[BL_WSUM].p;
+    slk_prof_begin(ctx, SLK_K_SCORE, s);
+    hipLaunchKernelGGL(k_weight_partials, dim3(slk_grid_for(ctx, (size_t)n_mb * segs * 256, 256)), dim3(256), 0, s,
+                       c.weights + chunk_begin(p, ck), nc, bsz, segs, wpart);
+    SLK_LAUNCH_CHECK(ctx, "k_weight_partials");
+    hipLaunchKernelGGL(k_weight_sums, dim3(slk_grid_for(ctx, (size_t)n_mb * 256, 256)), dim3(256), 0, s, (const double *)wpart, n_mb,
+                       segs, wsum);
+    SLK_LAUNCH_CHECK(ctx, "k_weight_sums");
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
 static int run_passes(slk_ctx *ctx, const train_plan &p, const train_call &c, const train_kernels &k, train_run &run, size_t ck, slk_prep_bufs &pb, hipStream_t s) {
     int rc;
     const uint32_t nc = chunk_len(p, c, ck), bsz = (uint32_t)p.bsz;
@@ -1784,6 +1912,7 @@ static int run_passes(slk_ctx *ctx, const train_plan &p, const train_call &c, co
     const int ugm = p.side && ctx->opt_user_grid_mult > 6 ? 6 : ctx->opt_user_grid_mult;
     minibatch mb;
     mb.ugm = ugm;
+    if (p.weighted && (rc = weight_sums(ctx, p, c, ck, s))) return rc;
     for (uint32_t b0 = 0; b0 < nc; b0 += bsz, ++run.mb_global) {
         const uint32_t b1 = (nc - b0 < bsz) ? nc : b0 + bsz, bm = b1 - b0;
         mb.b0 = b0, mb.b1 = b1, mb.bm = bm;
@@ -1792,7 +1921,9 @@ static int run_passes(slk_ctx *ctx, const train_plan &p, const train_call &c, co
         a.end = b1;
         a.ibegin = b0 * (uint32_t)p.NP;
         a.iend = b1 * (uint32_t)p.NP;
-        a.inv_b = 1.0f / (float)bm;
+        // (weighted: the loss kernels of score_stage divide by the minibatch's weight sum themselves -- dL/dscore and the loss
+        // partials alike -- and nothing else of a staged call reads inv_b but the finalisation of d_mb_loss in the item pass)
+        a.inv_b = p.weighted ? 1.0f : 1.0f / (float)bm;
         a.mb_loss_out = c.mb_loss + run.mb_global;
         slk_set_opt_coeffs(a, c.optim);
         // Round 6 (profiles/r06_mall_ab.jsonl): a minibatch whose records are as large as the Infinity Cache (2^20 x 256 B
@@ -1981,7 +2112,7 @@ static int run_training(slk_ctx *ctx, const train_call &c) {
     // a chunk prepared ahead by slk_bilinear_prefetch: it must be THIS call's first chunk (its negatives are already drawn)
     // (a call that draws nothing -- negatives handed in, explicit feedback -- cannot be confused with the prepared one: it drops
     // the chunk instead of refusing; fit() of another model after one that left its loop by an exception)
-    if (ctx->pf.valid && (c.neg_in || p.expl)) ctx->pf.valid = false;
+    if (ctx->pf.valid && (c.neg_in || p.expl || p.weighted)) ctx->pf.valid = false;  // (a weighted call is never the prepared one)
     const bool have0 = ctx->pf.valid;
     ctx->pf.valid = false;
     if (have0 && (!p.side || p.epoch_route || ctx->pf.users != (const void *)c.users || ctx->pf.items != (const void *)c.items ||

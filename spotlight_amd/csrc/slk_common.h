@@ -121,6 +121,8 @@ enum slk_extra_slot {
     // offsets check's flag.  Nothing survives a call, but EV_TOPK / EV_TOPK_FLAG have numbers of their own, not SH_UIT / SH_GPOS:
     // slk_shard_topk may run on a sharded trainer's ctx between a chunk's begin and its passes
     EV_REP = 24, EV_RBIAS, EV_ST = 37, EV_CNT = 39, EV_TOPK = 50, EV_TOPK_FLAG,
+    // slk_bilinear.hip, a weighted training call: the float64 weight sums of a chunk's minibatches and their per-segment partials
+    BL_WSUM = 52, BL_WPART,
     SLK_EXTRA_END  // (the slots above are the highest in use)
 };
 static_assert(SLK_EXTRA_END <= SLK_EXTRA_BUFS, "slk_ctx::extra holds every slot of slk_extra_slot");

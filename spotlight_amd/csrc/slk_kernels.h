@@ -289,6 +289,33 @@ __device__ __forceinline__ void slk_explicit_loss(int loss_kind, float sc, float
     }
 }
 
+// Interaction weights (slk_bilinear_train_weighted): the minibatch loss is sum(w_i l_i) / W, W = sum(w_i) formed in float64
+// and rounded ONCE to fp32 (Wf); inv_W = 1.0f / Wf.  dL/dscore is the unweighted factor without its 1 / B, times w_i, times
+// inv_W, in that order -- so that all-ones weights give 1 / B and today's products bit for bit, and a power of two on every
+// weight cancels exactly (w_i and W scale together; the products below hold one rounding each side of the scale).
+__device__ __forceinline__ float slk_weight_scale(float g_unit, float w, float inv_W) { return (g_unit * w) * inv_W; }
+
+// slk_explicit_loss with a weight: l is the unweighted term (the caller sums w * l in double).  Poisson and logistic keep the
+// SHAPE of slk_explicit_loss's own dL/dscore, so that w == 1 gives its bits: poisson with w * inv_W in inv_b's place,
+// logistic the division by the rounded sum where slk_explicit_loss divides by (float)bm.
+__device__ __forceinline__ void slk_explicit_loss_weighted(int loss_kind, float sc, float r, float w, float inv_W, float Wf,
+                                                           float &l, float &g) {
+    if (loss_kind == SLK_LOSS_REGRESSION) {
+        const float diff = r - sc;
+        l = diff * diff;
+        g = -slk_weight_scale(2.0f * diff, w, inv_W);
+    } else if (loss_kind == SLK_LOSS_POISSON) {
+        const float p = expf(sc), s = w * inv_W;
+        l = p - r * logf(p);
+        g = (s + ((-s) * r) / p) * p;
+    } else {
+        const float t = r < 0.0f ? 0.0f : (r > 1.0f ? 1.0f : r);
+        const float mx = -sc > 0.0f ? -sc : 0.0f;
+        l = (1.0f - t) * sc + (mx + logf(expf(-mx) + expf(-sc - mx)));
+        g = ((slk_sigmoid(sc) - t) * w) / Wf;
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // ITEM PASS
 // ---------------------------------------------------------------------------------------
@@ -1010,10 +1037,14 @@ static __global__ __launch_bounds__(256) void k_item_multi_flags(const uint32_t 
 template <int UNUSED>
 __global__ __launch_bounds__(256) void k_adaptive_select(const float *sk, float *gk, uint32_t k0, uint32_t bm,
                                                          int nn, float inv_b, double *loss_partial,
-                                                         const uint32_t *qk, uint32_t *live) {
+                                                         const uint32_t *qk, uint32_t *live, const float *w,
+                                                         const double *wsum) {
     __shared__ double red[256];
     const int NP = nn + 1;
     double lsum = 0.0;
+    // w (optional; interaction weights, chunk-local as sk is): column c carries the weight of ITS positive, interaction k0 + c,
+    // on the positive and on the selected negative alike; *wsum = the minibatch's float64 weight sum (slk_weight_scale)
+    const float inv_W = w ? 1.0f / (float)*wsum : 0.0f;
     for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < bm; c += gridDim.x * 256) {
         const float sp = sk[(size_t)(k0 + c) * NP];
         float best = 0.0f;
@@ -1028,8 +1059,9 @@ __global__ __launch_bounds__(256) void k_adaptive_select(const float *sk, float 
             }
         }
         const float x = best - sp + 1.0f;
-        lsum += (double)(x > 0.0f ? x : 0.0f);
-        const float g = x >= 0.0f ? inv_b : 0.0f;
+        const float wc = w ? w[k0 + c] : 1.0f;
+        lsum += w ? (double)wc * (double)(x > 0.0f ? x : 0.0f) : (double)(x > 0.0f ? x : 0.0f);
+        const float g = x >= 0.0f ? (w ? slk_weight_scale(1.0f, wc, inv_W) : inv_b) : 0.0f;
         gk[(size_t)(k0 + c) * NP] = -g;
         // the column's n draws are written by this thread alone, and the columns partition the n*B draws: every entry of
         // gk gets its value here (no memset before the launch)
@@ -1045,7 +1077,8 @@ __global__ __launch_bounds__(256) void k_adaptive_select(const float *sk, float 
         }
     }
     const double tot = slk_block_sum_256(lsum, red);
-    if (threadIdx.x == 0) loss_partial[blockIdx.x] = tot;
+    // (weighted: the partials leave already divided by the weight sum -- the item pass's finalisation then runs with inv_b = 1)
+    if (threadIdx.x == 0) loss_partial[blockIdx.x] = w ? tot * (double)inv_W : tot;
 }
 
 

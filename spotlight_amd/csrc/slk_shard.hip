@@ -847,7 +847,8 @@ SLK_EXPORT int slk_shard_adaptive_select(slk_ctx *ctx, int64_t global_batch, int
     const unsigned sgrid = slk_grid_for(ctx, (size_t)global_batch, 256);
     slk_prof_begin(ctx, SLK_K_SCORE, s);
     hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, d_scores, d_gk, 0u, (uint32_t)global_batch, (int)n_neg,
-                       inv_b, (double *)ctx->losspart.p, (const uint32_t *)nullptr, (uint32_t *)nullptr);
+                       inv_b, (double *)ctx->losspart.p, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const float *)nullptr,
+                       (const double *)nullptr);  // (no interaction weights on the row-sharded path)
     SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
     slk_prof_end(ctx, s);
     // every rank has computed the whole minibatch's loss; the ranks' shares must ADD UP to it: one rank reports it

@@ -22,13 +22,17 @@ from spotlight_amd.torch_utils import set_seed
 class _ExplicitEpochs(object):
     """What the schedules of spotlight_amd/_epochs.py ask of the explicit-feedback model: the shuffle of the three arrays and
     slk_bilinear_train_explicit.  `lane_stream`: the raw stream of the two-lane schedule's prep lane (two sets of epoch
-    buffers, the ratings converted on that stream); None under the serial schedule (one set, this thread's stream)."""
+    buffers, the ratings converted on that stream); None under the serial schedule (one set, this thread's stream).
+    `sources`: users, items, the ratings' int64 carriers and -- a fit on interaction weights (use_weights=True) -- the weights';
+    a set of epoch buffers is one buffer per source, then the float32 values read back out of each carrier."""
 
     def __init__(self, model, binding, tables, sources, device, lane_stream=None):
         self.binding, self.tables, self.sources, self.n = binding, tables, sources, sources[0].numel()
         self.call = (self.n, model._batch_size, model._loss)
         self.mb_loss = torch.empty((self.n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
-        self.slots = [[torch.empty_like(d) for d in sources] + [torch.empty(self.n, dtype=torch.float32, device=device)]
+        self.floats = len(sources) - 2
+        self.slots = [[torch.empty_like(d) for d in sources] +
+                      [torch.empty(self.n, dtype=torch.float32, device=device) for _ in range(self.floats)]
                       for _ in range(1 if lane_stream is None else 2)]
         self.d_perm = torch.empty(self.n, dtype=torch.int64, device=device)
         self.side = (torch.cuda.ExternalStream(lane_stream, device=device)
@@ -40,24 +44,35 @@ class _ExplicitEpochs(object):
                                      [(src, dst, 1) for src, dst in zip(self.sources, slot)], stream)
         # (on the prep lane's stream where there is one: the state read-back that follows then covers the conversion too)
         with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
-            slot[3].view(torch.int32).copy_(slot[2])  # the float32 bit patterns back out of their int64 carriers
+            for k in range(self.floats):  # the float32 bit patterns back out of their int64 carriers
+                slot[2 + self.floats + k].view(torch.int32).copy_(slot[2 + k])
 
     def train(self, engine, stream, epoch_num):
-        d_users, d_items, _, d_ratings = self.slots[epoch_num % len(self.slots)]
+        slot = self.slots[epoch_num % len(self.slots)]
+        d_users, d_items, d_ratings = slot[0], slot[1], slot[2 + self.floats]
         ostruct = self.binding.as_struct()
-        engine.bilinear_train_explicit(self.tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), d_ratings.data_ptr(),
-                                       *self.call, self.mb_loss.data_ptr(), stream=stream)
+        if self.floats == 2:
+            n, batch_size, loss = self.call
+            engine.bilinear_train_weighted(self.tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), slot[5].data_ptr(), n,
+                                           batch_size, loss, 0, self.mb_loss.data_ptr(), d_ratings=d_ratings.data_ptr(),
+                                           stream=stream)
+        else:
+            engine.bilinear_train_explicit(self.tables, ostruct, d_users.data_ptr(), d_items.data_ptr(), d_ratings.data_ptr(),
+                                           *self.call, self.mb_loss.data_ptr(), stream=stream)
         self.binding.store_steps(ostruct.step)
 
 
 class ExplicitFactorizationModel(ImplicitFactorizationModel):
     """Explicit-feedback matrix factorization (ratings).  Parameters follow
     spotlight/factorization/explicit.py:68-79; `use_cuda` is accepted for signature compatibility
-    (the model always lives on the HIP device), `representation` may be a BilinearNet."""
+    (the model always lives on the HIP device), `representation` may be a BilinearNet.  `use_weights` (not in the reference):
+    False ignores `Interactions.weights`, as the reference does; True fits the weighted regression / likelihood
+    sum(w_i * l_i) / sum(w_i) per minibatch (ImplicitFactorizationModel's docstring: same checks, same schedule, same
+    RandomState as the unweighted fit)."""
 
     def __init__(self, loss='regression', embedding_dim=32, n_iter=10, batch_size=256, l2=0.0,
                  learning_rate=1e-2, optimizer_func=None, use_cuda=False, representation=None, sparse=False,
-                 random_state=None):
+                 random_state=None, use_weights=False):
 
         assert loss in ('regression', 'poisson', 'logistic')
 
@@ -72,6 +87,7 @@ class ExplicitFactorizationModel(ImplicitFactorizationModel):
         self._sparse = sparse
         self._optimizer_func = optimizer_func
         self._random_state = random_state or np.random.RandomState()
+        self._use_weights = bool(use_weights)
 
         self._num_users = None
         self._num_items = None
@@ -99,6 +115,7 @@ class ExplicitFactorizationModel(ImplicitFactorizationModel):
         if interactions.ratings is None:
             # the reference fails inside shuffle() when it indexes None (explicit.py:201-204)
             raise TypeError("'NoneType' object is not subscriptable: explicit feedback needs interactions.ratings")
+        iw = _host.interaction_weights(getattr(self, '_use_weights', False), interactions)  # (ValueError before anything is drawn)
 
         binding = self._bind()
         device = self._net.tables()[0].device
@@ -108,12 +125,14 @@ class ExplicitFactorizationModel(ImplicitFactorizationModel):
         # ids and ratings go to the device once; the ratings ride through the shuffle as int64 bit
         # patterns (slk_gather_rows_i64 moves 8-byte elements)
         ratings = np.ascontiguousarray(interactions.ratings, dtype=np.float32)
-        sources = [_host.ids_to_device(user_ids, device), _host.ids_to_device(item_ids, device),
-                   torch.from_numpy(ratings).to(device).view(torch.int32).to(torch.int64)]
+        sources = [_host.ids_to_device(user_ids, device), _host.ids_to_device(item_ids, device), _host.float_carrier(ratings, device)]
+        if iw is not None:  # the weights ride the shuffle beside the ratings
+            sources.append(_host.float_carrier(iw, device))
         # The reference's README example fits MovieLens-100K with batch_size 256: training draws nothing from the RandomState,
         # so epochs of that scale shuffle epoch e + 1 on a second slk_ctx / HIP stream while epoch e trains (_epochs.run_two_lane).
         # Same permutations, same RandomState afterwards, bit-identical tables.
-        if self._n_iter > 1 and n <= _host._PIPELINE_MAX_DRAWS:
+        # (a fit on interaction weights: the two-lane schedule at every size)
+        if iw is not None or (self._n_iter > 1 and n <= _host._PIPELINE_MAX_DRAWS):
             lane = _host._prep_lane_for(device)
             job = _ExplicitEpochs(self, binding, self._slk_tables(), sources, device, lane_stream=lane[1])
             return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)

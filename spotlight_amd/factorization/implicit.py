@@ -4,6 +4,7 @@ Same constructor, fit(), predict(), error messages and random-state behaviour as
 reference; everything inside the epoch loop (negative sampling, both forward passes, loss,
 backward, optimizer update) is one C-ABI call into csrc/libspotlight_hip.so per epoch.
 """
+import contextlib
 import inspect
 
 import numpy as np
@@ -92,6 +93,33 @@ def _model_device():
         raise RuntimeError('spotlight_amd needs a HIP device (MI355X): torch.cuda.is_available() '
                            'is False and there is no CPU fallback')
     return torch.device('cuda', torch.cuda.current_device())
+
+
+def interaction_weights(use_weights, interactions):
+    """The float32 weights a fit() with use_weights=True trains on (None without it: interactions.weights is ignored, as the
+    reference ignores it): one per interaction, finite and strictly positive -- an interaction of weight 0 is one to drop, and a
+    minibatch whose weights sum to 0 has no loss.  ValueError otherwise; draws nothing."""
+    if not use_weights:
+        return None
+    if interactions.weights is None:
+        raise ValueError('use_weights=True needs interactions.weights')
+    weights = np.asarray(interactions.weights)
+    if weights.ndim != 1 or len(weights) != len(interactions.user_ids):
+        raise ValueError('interactions.weights: one weight per interaction is needed')
+    try:
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError('interactions.weights must be numbers')
+    if not np.isfinite(weights).all():
+        raise ValueError('interactions.weights must be finite (float32)')
+    if weights.size and weights.min() <= 0:
+        raise ValueError('interactions.weights must be strictly positive: drop an interaction instead of weighting it 0')
+    return weights
+
+
+def float_carrier(values, device):
+    """float32 values as the int64 bit patterns slk_gather_rows_i64 moves through the epoch shuffle (8-byte elements)."""
+    return torch.from_numpy(values).to(device).view(torch.int32).to(torch.int64)
 
 
 def _state_tensor(state, key, like):
@@ -236,24 +264,35 @@ class _ImplicitEpochs(object):
         self.dist = getattr(model, '_item_distribution', None)  # None: uniform negatives
         self.call = (n, model._batch_size, model._loss, model._num_negative_samples)
         self.mb_loss = torch.empty((n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
-        self.slots, self.scopes, self.sources = [], [], None
+        self.slots, self.scopes, self.sources, self.weighted, self.side = [], [], None, False, None
 
     def reserve(self, engine, stream):
         engine.bilinear_reserve(self.tables, self.binding.as_struct(), *self.call, stream=stream)
 
-    def own_slots(self, sources, nn):
-        """Two-lane schedule: two sets of epoch buffers, shuffled from the uploaded `sources`."""
-        self.sources = sources
+    def own_slots(self, sources, nn, lane_stream=None):
+        """Two-lane schedule: two sets of epoch buffers, shuffled from the uploaded `sources` -- (users, items) or, for a fit on
+        interaction weights, (users, items, the weights' int64 carriers); such a set then ends with the carriers' buffer and
+        the float32 weights read back out of it on the prep lane's stream (`lane_stream`)."""
+        self.sources, self.weighted = sources, len(sources) > 2
+        extra = lambda: ((torch.empty_like(sources[2]), torch.empty(self.n, dtype=torch.float32, device=self.device))
+                         if self.weighted else ())
         self.slots = [(torch.empty_like(sources[0]), torch.empty_like(sources[1]),
-                       torch.empty(self.n * nn, dtype=torch.int64, device=self.device)) for _ in range(2)]
+                       torch.empty(self.n * nn, dtype=torch.int64, device=self.device)) + extra() for _ in range(2)]
+        if self.weighted and lane_stream is not None and self.device.type == 'cuda':
+            self.side = torch.cuda.ExternalStream(lane_stream, device=self.device)
         # (the permutation AFTER the epoch buffers, all of one size class in the caching allocator: allocated first it cost a
         # MovieLens-100K fit() 0.9 %, profiles/fit_driver_parent_vs_head.json, sessions 1 and 2)
         self.d_perm = torch.empty(self.n, dtype=torch.int64, device=self.device)
 
     def prepare(self, engine, stream, random_state, epoch_num):
-        d_users, d_items, d_neg = self.slots[epoch_num % 2]
+        slot = self.slots[epoch_num % 2]
+        d_neg = slot[2]
+        # (the weights travel with their interactions: a third array through the same permutation)
         _epochs.device_epoch_shuffle(engine, random_state, self.n, self.d_perm,
-                                     [(self.sources[0], d_users, 1), (self.sources[1], d_items, 1)], stream)
+                                     [(src, dst, 1) for src, dst in zip(self.sources, slot[:2] + slot[3:4])], stream)
+        if self.weighted:  # (on the prep lane's stream: the state read-back behind the negatives covers the conversion)
+            with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+                slot[4].view(torch.int32).copy_(slot[3])
         # one randint (one choice) per minibatch == one contiguous draw over the epoch (sampling.py:34)
         _sampling.draw_items(engine, self.num_items, d_neg.numel(), d_neg.data_ptr(), stream, self.dist)
 
@@ -273,8 +312,12 @@ class _ImplicitEpochs(object):
         slot = self.slots[epoch_num % len(self.slots)]
         d_neg = slot[2].data_ptr() if len(slot) > 2 else None  # (handed in under the two-lane schedule, else drawn by the call)
         ostruct = self.binding.as_struct()
-        engine.bilinear_train(self.tables, ostruct, slot[0].data_ptr(), slot[1].data_ptr(), *self.call, self.mb_loss.data_ptr(),
-                              d_neg_in=d_neg, stream=stream)
+        if self.weighted:
+            engine.bilinear_train_weighted(self.tables, ostruct, slot[0].data_ptr(), slot[1].data_ptr(), slot[4].data_ptr(),
+                                           *self.call, self.mb_loss.data_ptr(), d_neg_in=d_neg, stream=stream)
+        else:
+            engine.bilinear_train(self.tables, ostruct, slot[0].data_ptr(), slot[1].data_ptr(), *self.call,
+                                  self.mb_loss.data_ptr(), d_neg_in=d_neg, stream=stream)
         self.binding.store_steps(ostruct.step)
 
 
@@ -302,12 +345,20 @@ class ImplicitFactorizationModel(object):
       the model's RandomState, made on the device bit for bit (csrc/slk_rng.hip); fit() then prepares every epoch's
       negatives beside the epoch before it at every size (the two-lane schedule), and fold_in() draws from the distribution
       of the last fit().
+    * `use_weights` (not in the reference, which carries `Interactions.weights` and never reads them): False (default) ignores
+      the weights, as the reference does.  True: fit() minimises, per minibatch, sum(w_i * l_i) / sum(w_i) over the
+      per-interaction terms l_i of the loss (adaptive hinge: a column carries the weight of its positive) -- play counts, dwell
+      times, recency decay.  `interactions.weights` must then be given, finite and > 0 (ValueError before anything is drawn).
+      Shuffles, negatives and the RandomState are those of the unweighted fit; the weights ride the shuffle with their
+      interactions.  Such a fit runs the two-lane schedule at every size and opens neither training scope (item-bias shadow,
+      user-row ping-pong); dL/dscore is formed ahead of the user pass (include/spotlight_hip.h: slk_bilinear_train_weighted).
+      fold_in() stays unweighted.
     """
 
     def __init__(self, loss='pointwise', embedding_dim=32, n_iter=10, batch_size=256, l2=0.0,
                  learning_rate=1e-2, optimizer_func=None, use_cuda=False, representation=None,
                  sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
-                 negative_sampling_power=0.75):
+                 negative_sampling_power=0.75, use_weights=False):
 
         assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge')
         _sampling.check_negative_sampling(negative_sampling)
@@ -327,6 +378,7 @@ class ImplicitFactorizationModel(object):
         self._negative_sampling = negative_sampling
         self._negative_sampling_power = negative_sampling_power
         self._item_distribution = None  # sampling.ItemDistribution of the last fit() (None: uniform)
+        self._use_weights = bool(use_weights)
 
         self._num_users = None
         self._num_items = None
@@ -437,7 +489,10 @@ class ImplicitFactorizationModel(object):
         # non-uniform negatives are handed in at every size (the two-lane schedule): the three-stage pipeline's
         # slk_bilinear_prefetch draws uniform ones ahead of time
         weighted = not _sampling.is_uniform(getattr(self, '_negative_sampling', None))
-        small = weighted or (self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS)
+        # interaction weights (use_weights=True; a model pickled before the keyword existed has none): validated with the item
+        # weights, before anything is drawn.  They ride the two-lane schedule's shuffle at every size, too.
+        iw = interaction_weights(getattr(self, '_use_weights', False), interactions)
+        small = weighted or iw is not None or (self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS)
         # the id-range checks (implicit.py:169-182): four reductions over the host arrays, 12 ms at 2^25 ids.  On the large-epoch
         # path they run on worker threads beside the id upload and the first epoch's shuffle; their verdict is collected before
         # the first training call is enqueued (nothing the caller can observe has changed by then: the RandomState is restored,
@@ -451,7 +506,7 @@ class ImplicitFactorizationModel(object):
                                                               getattr(self, '_negative_sampling_power', 0.75), self._num_items,
                                                               item_ids)
         if autograd:
-            return self._fit_autograd(user_ids, item_ids, verbose)
+            return self._fit_autograd(user_ids, item_ids, verbose, iw)
         binding = self._bind()
         device = self._net.tables()[0].device
         engine = _engine_for(device)
@@ -471,7 +526,8 @@ class ImplicitFactorizationModel(object):
         # ids go to the device once (on a worker thread: the first epoch's permutation is drawn meanwhile); every epoch's
         # permutation x[shuffle_indices] of them (torch_utils.py:35-52) is computed there, bit-exact with numpy's Fisher-Yates
         if small:
-            job.own_slots(IdUpload([user_ids, item_ids], device).result(), nn)
+            sources = IdUpload([user_ids, item_ids], device).result()
+            job.own_slots(sources + ([float_carrier(iw, device)] if iw is not None else []), nn, lane_stream=lane[1])
             return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
         threaded = _PREFETCH and lane[0] is not engine and engine._lib is _native._LIB  # (the test harness's emulator is single-threaded)
         ids = _epochs.ShuffledIds(lane[0], lane[1], user_ids, item_ids, min(self._n_iter, 3 if _PREFETCH else 2), device)
@@ -487,10 +543,11 @@ class ImplicitFactorizationModel(object):
         return _epochs.run_three_stage(engine, stream, self._random_state, self._n_iter, verbose, job, ids, check,
                                        prefetch=_PREFETCH, threaded=threaded)
 
-    def _fit_autograd(self, user_ids, item_ids, verbose):
+    def _fit_autograd(self, user_ids, item_ids, verbose, weights=None):
         """The reference's epoch / minibatch loop (implicit.py:208-252, 254-275) for models without a fused path: host numpy
         shuffle and negatives from `random_state` (the reference's exact consumption of the stream), forward / loss /
-        backward / optimizer.step() as stock torch ops on the HIP device."""
+        backward / optimizer.step() as stock torch ops on the HIP device.  `weights` (use_weights=True): shuffled with the ids,
+        the minibatch loss is losses.py's weighted form."""
         from spotlight_amd import losses as _losses
         from spotlight_amd.sampling import sample_items
         from spotlight_amd.torch_utils import minibatch, shuffle
@@ -504,11 +561,13 @@ class ImplicitFactorizationModel(object):
                                                  p=self._item_distribution)).to(device)
 
         for epoch_num in range(self._n_iter):
-            users, items = shuffle(user_ids, item_ids, random_state=self._random_state)
-            user_ids_tensor = torch.from_numpy(np.ascontiguousarray(users).astype(np.int64)).to(device)
-            item_ids_tensor = torch.from_numpy(np.ascontiguousarray(items).astype(np.int64)).to(device)
+            arrays = shuffle(*((user_ids, item_ids) + ((weights,) if weights is not None else ())), random_state=self._random_state)
+            tensors = [torch.from_numpy(np.ascontiguousarray(x).astype(np.int64)).to(device) for x in arrays[:2]]
+            if weights is not None:
+                tensors.append(torch.from_numpy(np.ascontiguousarray(arrays[2])).to(device))
             epoch_loss, n_mb = 0.0, 0
-            for batch_user, batch_item in minibatch(user_ids_tensor, item_ids_tensor, batch_size=self._batch_size):
+            for batch in minibatch(*tensors, batch_size=self._batch_size):
+                batch_user, batch_item = batch[:2]
                 positive_prediction = self._net(batch_user, batch_item)
                 if self._loss == 'adaptive_hinge':
                     # implicit.py:266-275: users repeated user-major, ONE draw of B * n, scores viewed as [n, B]
@@ -520,7 +579,7 @@ class ImplicitFactorizationModel(object):
                 else:
                     negative_prediction = self._net(batch_user, negatives_for(batch_user, len(batch_user)))
                 self._optimizer.zero_grad()
-                loss = loss_func(positive_prediction, negative_prediction)
+                loss = loss_func(positive_prediction, negative_prediction, weights=batch[2] if weights is not None else None)
                 epoch_loss += loss.item()
                 loss.backward()
                 self._optimizer.step()
@@ -640,7 +699,8 @@ class ImplicitFactorizationModel(object):
         Plain tables with Adam / Adagrad / SparseAdam / plain SGD: one fused call (csrc/slk_foldin.hip).  An item
         BloomEmbedding (materialised once), any other optimizer_func, or a custom representation with `item_embeddings` /
         `item_biases`: the same steps through autograd (spotlight_amd/foldin.py).  A user BloomEmbedding has no per-user row:
-        TypeError.  Refused inside an open fit() scope whose item biases are shadowed, as predict() is."""
+        TypeError.  Refused inside an open fit() scope whose item biases are shadowed, as predict() is.
+        Interaction weights do not enter: a model built with use_weights=True folds in unweighted (`interactions.weights` is not read)."""
         from spotlight_amd import foldin as _foldin
         return _foldin.fold_in(self, interactions, n_iter, init, negatives)
 

@@ -333,7 +333,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
     torch's CPU generator in the reference's order and this rank keeps rows `rank::world`.
 
     All four losses (adaptive hinge: a score phase and a selection over the whole minibatch in front of the user pass,
-    ShardedBilinearTrainer.run_chunk).  Restriction of the exchange path: plain (non-bloom) tables.
+    ShardedBilinearTrainer.run_chunk).  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
+    sharded yet: use_weights=True raises ValueError at construction.
 
     Evaluation runs shard by shard as well: evaluation.mrr_score (_fused_ranks), precision_recall_score (_batch_scores) and
     predict(user) sweep every rank's own item rows and combine the ranks' target scores (MAX), integer counts (SUM) or score
@@ -343,6 +344,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
     def __init__(self, *args, **kwargs):
         self._group = kwargs.pop('group', None)
         super(ShardedImplicitFactorizationModel, self).__init__(*args, **kwargs)
+        if self._use_weights:
+            raise ValueError('use_weights=True is not supported by the row-sharded path: interaction weights are not sharded yet')
         if self._representation is not None:
             raise NotImplementedError('custom representations are not supported by the row-sharded path')
         if self._negative_sampling is not None and not (isinstance(self._negative_sampling, str) and self._negative_sampling == 'uniform'):

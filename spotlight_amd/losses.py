@@ -6,6 +6,10 @@ which follow the same formulas operation by operation.
 
 Implicit-feedback losses take (positive_predictions, negative_predictions[, mask]); with a mask
 (sequence models: mask = sequence != 0) the mean is over the unmasked entries only.
+
+`weights` (not in the reference; every loss, default None = the reference's mean): one weight per interaction, the loss is
+sum(w_i * l_i) / sum(w_i) over the per-interaction terms l_i -- what fit() of a model built with use_weights=True minimises
+(include/spotlight_hip.h: slk_bilinear_train_weighted).  Under adaptive hinge the weight of a column is the weight of its positive.
 """
 import torch
 import torch.nn.functional as F
@@ -13,49 +17,54 @@ import torch.nn.functional as F
 from spotlight_amd.torch_utils import assert_no_grad
 
 
-def _masked_mean(values, mask):
-    if mask is None:
+def _masked_mean(values, mask, weights=None):
+    if mask is None and weights is None:
         return values.mean()
-    weights = mask.float()
+    if weights is None:
+        weights = mask.float()
+    elif mask is not None:
+        weights = weights * mask.float()
     return (values * weights).sum() / weights.sum()
 
 
-def pointwise_loss(positive_predictions, negative_predictions, mask=None):
+def pointwise_loss(positive_predictions, negative_predictions, mask=None, weights=None):
     """Logistic loss: (1 - sigmoid(pos)) + sigmoid(neg)   (losses.py:18-50)."""
-    return _masked_mean((1.0 - torch.sigmoid(positive_predictions)) + torch.sigmoid(negative_predictions), mask)
+    return _masked_mean((1.0 - torch.sigmoid(positive_predictions)) + torch.sigmoid(negative_predictions), mask, weights)
 
 
-def bpr_loss(positive_predictions, negative_predictions, mask=None):
+def bpr_loss(positive_predictions, negative_predictions, mask=None, weights=None):
     """Spotlight's BPR variant: 1 - sigmoid(pos - neg) -- not -log sigmoid   (losses.py:53-90)."""
-    return _masked_mean(1.0 - torch.sigmoid(positive_predictions - negative_predictions), mask)
+    return _masked_mean(1.0 - torch.sigmoid(positive_predictions - negative_predictions), mask, weights)
 
 
-def hinge_loss(positive_predictions, negative_predictions, mask=None):
+def hinge_loss(positive_predictions, negative_predictions, mask=None, weights=None):
     """max(0, neg - pos + 1)   (losses.py:93-124)."""
-    return _masked_mean(torch.clamp(negative_predictions - positive_predictions + 1.0, 0.0), mask)
+    return _masked_mean(torch.clamp(negative_predictions - positive_predictions + 1.0, 0.0), mask, weights)
 
 
-def adaptive_hinge_loss(positive_predictions, negative_predictions, mask=None):
+def adaptive_hinge_loss(positive_predictions, negative_predictions, mask=None, weights=None):
     """Hinge loss against the highest-scoring of several sampled negatives: negative_predictions has the
     candidates along dim 0   (losses.py:127-166)."""
     hardest, _ = negative_predictions.max(0)
-    return hinge_loss(positive_predictions, hardest.squeeze(), mask=mask)
+    return hinge_loss(positive_predictions, hardest.squeeze(), mask=mask, weights=weights)
 
 
-def regression_loss(observed_ratings, predicted_ratings):
+def regression_loss(observed_ratings, predicted_ratings, weights=None):
     """Mean squared error   (losses.py:169-191)."""
     assert_no_grad(observed_ratings)
-    return ((observed_ratings - predicted_ratings) ** 2).mean()
+    return _masked_mean((observed_ratings - predicted_ratings) ** 2, None, weights)
 
 
-def poisson_loss(observed_ratings, predicted_ratings):
+def poisson_loss(observed_ratings, predicted_ratings, weights=None):
     """Poisson negative log-likelihood up to a constant: pred - obs * log(pred)   (losses.py:194-216)."""
     assert_no_grad(observed_ratings)
-    return (predicted_ratings - observed_ratings * torch.log(predicted_ratings)).mean()
+    return _masked_mean(predicted_ratings - observed_ratings * torch.log(predicted_ratings), None, weights)
 
 
-def logistic_loss(observed_ratings, predicted_ratings):
+def logistic_loss(observed_ratings, predicted_ratings, weights=None):
     """Binary cross-entropy with logits; observed ratings are -1 / +1   (losses.py:219-244)."""
     assert_no_grad(observed_ratings)
     targets = torch.clamp(observed_ratings, 0, 1)
-    return F.binary_cross_entropy_with_logits(predicted_ratings, targets, reduction='mean')
+    if weights is None:
+        return F.binary_cross_entropy_with_logits(predicted_ratings, targets, reduction='mean')
+    return _masked_mean(F.binary_cross_entropy_with_logits(predicted_ratings, targets, reduction='none'), None, weights)
