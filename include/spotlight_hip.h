@@ -47,7 +47,26 @@ enum slk_loss {
     /* explicit feedback (spotlight/losses.py:169-244), slk_bilinear_train_explicit only */
     SLK_LOSS_REGRESSION = 4,
     SLK_LOSS_POISSON = 5,
-    SLK_LOSS_LOGISTIC = 6
+    SLK_LOSS_LOGISTIC = 6,
+    /* WARP (added to ABI 14: one new loss id, nothing existing changes, SLK_ABI_VERSION stays): the rank-weighted hinge on
+     * the FIRST violating negative (WSABIE; LightFM's loss='warp').  An implicit-feedback COLUMN loss like adaptive hinge: the
+     * very same n = n_neg draws per positive in the very same view(n, B) layout (factorization/implicit.py:266-275; column c
+     * of a minibatch of bm positives holds flat draws r * bm + c, r = 0 .. n-1), all drawn and scored up front -- no
+     * data-dependent early stop, so the draws stay numpy-exact, the generator ends where an adaptive-hinge call with the same
+     * n leaves it, and a step stays a pure function of its inputs.  Only the per-column rule differs.  With I =
+     * tables->num_items, sp the positive's score and s_0 .. s_{n-1} the column's candidate scores in row order:
+     *   x_r = s_r - sp + 1.0f                   (fp32, as the hinge forms it)
+     *   t   = the smallest r with x_r > 0       (strict; a NaN does not violate)
+     *   no such r: l_c = 0, no gradient, the column is not live (both live payloads ~0u, as for an inactive hinge)
+     *   else  w   = logf(fmaxf(1.0f, (float)((I - 1) / (t + 1))))     integer division: LightFM's floor((I-1) / tries)
+     *         l_c = w * x_t,   dL/dsp = -w * inv_b,   dL/ds_t = +w * inv_b,   every other candidate 0
+     *         (w == 0, i.e. (I-1)/(t+1) <= 1: g == 0, the column is not live)
+     * minibatch loss = sum_c l_c / bm (the l_c summed in double).  With interaction weights (slk_bilinear_train_weighted) the
+     * column carries the weight w_c of its positive: g = (w * w_c) * inv_W, loss = sum(w_c l_c) / W.
+     * The rank estimate assumes uniform draws; under a weighted sampler it is a popularity-weighted rank.
+     * Accepted by slk_bilinear_train / _reserve / _prefetch / _train_weighted and slk_bilinear_foldin (n_neg >= 1); the
+     * explicit, sequence (PoolNet) and row-sharded entries refuse it with SLK_EINVAL. */
+    SLK_LOSS_WARP = 7
 };
 
 /* Optimizers the reference can instantiate (factorization/implicit.py:143-150):
@@ -771,7 +790,7 @@ int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_row
  *                       permutation of the users;
  *   step composition    one call with n_steps = T == T calls with n_steps = 1, the state carried in the caller's arrays.
  * Ids are NOT range-checked (as in slk_bilinear_train; spotlight_amd checks them on the host).  Refused with SLK_EINVAL: a NULL
- * required pointer, n_steps < 1, n_new_users < 1, n < 0, an explicit-feedback loss, n_neg < 1 under adaptive hinge, a dim without
+ * required pointer, n_steps < 1, n_new_users < 1, n < 0, an explicit-feedback loss, n_neg < 1 under adaptive hinge or warp, a dim without
  * a row layout, a bloom table on either side, item biases inside an open bias-shadow scope.  Nothing is retained, nothing is
  * allocated (no scratch at all), no host wait; profiled under SLK_K_USER_PASS. */
 int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_off, const int64_t *d_items,

@@ -1213,8 +1213,9 @@ SLK_EXPORT int slk_bilinear_train_explicit(slk_ctx *ctx, const slk_tables *table
                                            const int64_t *d_users, const int64_t *d_items, const float *d_ratings,
                                            int64_t n, int64_t batch_size, int32_t loss, float *d_mb_loss,
                                            void *stream) {
-    if (ctx && (loss < SLK_LOSS_REGRESSION || loss > SLK_LOSS_LOGISTIC))
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: loss kind %d is not regression/poisson/logistic", loss);
+    if (ctx && !slk_loss_is_explicit(loss))
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: loss kind %d%s is not regression/poisson/logistic", loss,
+                        loss == SLK_LOSS_WARP ? " (warp)" : "");
     if (ctx && n > 0 && !d_ratings) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: d_ratings is NULL");
     return run_training(ctx, {train_call::TRAIN, tables, optim, d_users, d_items, d_ratings, nullptr, nullptr, d_mb_loss, n,
                               batch_size, loss, 0, (hipStream_t)stream});
@@ -1248,10 +1249,11 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
     if ((rc = slk_check_optim(ctx, optim, 15u))) return rc;
     if (n < 0 || c.batch_size < 1) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: n %lld batch_size %lld",
                                                    (long long)n, (long long)c.batch_size);
-    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_LOGISTIC)
+    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_WARP)
         return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", c.loss);
-    p.adaptive = c.loss == SLK_LOSS_ADAPTIVE_HINGE;
-    p.expl = c.loss >= SLK_LOSS_REGRESSION;
+    // (`adaptive`: a COLUMN loss -- adaptive hinge or warp; they differ in k_adaptive_select's rule alone)
+    p.adaptive = slk_loss_is_column(c.loss);
+    p.expl = slk_loss_is_explicit(c.loss);
     if (p.expl != (c.ratings != nullptr) && !reserve)
         return slk_fail(ctx, SLK_EINVAL, "ratings go with (and only with) the regression/poisson/logistic losses");
     p.weighted = c.weights != nullptr;
@@ -1762,7 +1764,8 @@ static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, c
     } else {
         hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, f32p(ctx->gk), mb.b0, mb.bm,
                            p.nn, a.inv_b, (double *)ctx->losspart.p, p.late ? (const uint32_t *)pb.ipay[0].p : (const uint32_t *)nullptr,
-                           p.late ? u32p(ctx->extra[BL_LIVE]) : (uint32_t *)nullptr, wts, wsum);
+                           p.late ? u32p(ctx->extra[BL_LIVE]) : (uint32_t *)nullptr, wts, wsum, (int)c.loss,
+                           (uint32_t)c.tables->num_items);
         SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
     }
     a.n_loss_partial = (int)sgrid;

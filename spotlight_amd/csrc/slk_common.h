@@ -12,6 +12,13 @@
 #define SLK_EAGAIN_EPOCH 1  // internal: the persistent route declined a chunk, take the launch path
 #define SLK_EXPORT extern "C" __attribute__((visibility("default")))
 
+// The loss ids by family (include/spotlight_hip.h).  Explicit feedback is 4..6; the COLUMN losses -- 1 + n_neg lookups per
+// interaction, one selection per column of the minibatch's [n, B] candidate matrix, at most two live occurrences per column --
+// are adaptive hinge and warp; every other implicit loss is a one-negative pair loss.
+static inline bool slk_loss_is_explicit(int loss) { return loss >= SLK_LOSS_REGRESSION && loss <= SLK_LOSS_LOGISTIC; }
+static inline bool slk_loss_is_column(int loss) { return loss == SLK_LOSS_ADAPTIVE_HINGE || loss == SLK_LOSS_WARP; }
+static inline const char *slk_column_loss_name(int loss) { return loss == SLK_LOSS_WARP ? "warp" : "adaptive hinge"; }
+
 // Occupancy target of a kernel in waves per SIMD (caps its VGPR budget at 512 / n).  hipcc only;
 // the test harness's host build of these sources ignores it.
 #if defined(__HIPCC__)

@@ -342,11 +342,14 @@ __device__ __forceinline__ void slk_epoch_item_phase(const slk_epoch_args &e, co
     }
 }
 
-enum { SLK_EMODE_PAIR = 0, SLK_EMODE_EXPLICIT = 1, SLK_EMODE_ADAPTIVE = 2 };
+// (WARP: the ADAPTIVE mode with the other column rule.  A mode of its own, not a run-time branch: with the loss kind read from
+// the arguments the adaptive-hinge instantiations grew by 1-2 VGPRs and 9-21 spilled SGPRs in the gfx950 build)
+enum { SLK_EMODE_PAIR = 0, SLK_EMODE_EXPLICIT = 1, SLK_EMODE_ADAPTIVE = 2, SLK_EMODE_WARP = 3 };
 
 template <int VEC, int G, int UPD, int MODE>
 __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args e) {
-    constexpr bool EXPL = MODE == SLK_EMODE_EXPLICIT, ADP = MODE == SLK_EMODE_ADAPTIVE;
+    constexpr bool EXPL = MODE == SLK_EMODE_EXPLICIT, ADP = MODE == SLK_EMODE_ADAPTIVE || MODE == SLK_EMODE_WARP;
+    constexpr int COLUMN_LOSS = MODE == SLK_EMODE_WARP ? SLK_LOSS_WARP : SLK_LOSS_ADAPTIVE_HINGE;
     const uint32_t NP = ADP ? (uint32_t)e.NP : (EXPL ? 1u : 2u);  // score pairs (= item occurrences) per interaction
     HIP_DYNAMIC_SHARED(double, s_wave_sums)      // [4] per-wave loss sums (unused slots stay 0) + the barrier's two flag words
     int *s_flags = reinterpret_cast<int *>(s_wave_sums + 4);
@@ -491,9 +494,10 @@ __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args 
                     // dL/dscore of this interaction's 1 + n pairs.  Pair 0 (the positive) belongs to column kc of the
                     // minibatch's [n, B] candidate matrix; draw j is entry f = kc * n + j of the flat n * B draws, which the
                     // reference's view(n, B) puts in row f / B of column f % B (implicit.py:266-275).  Lane s evaluates the
-                    // column of pair s as k_adaptive_select does -- the positive's score, the n candidates, first maximum wins,
-                    // x = best - positive + 1, g = 1/B where x >= 0 -- and keeps the pair's share: -g for the positive, g for
-                    // the selected draw, 0 for the others.  Column kc's hinge term is counted here, once.
+                    // column of pair s as k_adaptive_select does -- the positive's score, the n candidates, the loss kind's rule
+                    // (slk_column_select: adaptive hinge the first maximum, g = 1/B where x >= 0; warp the first violator, g =
+                    // weight/B) -- and keeps the pair's share: -g for the positive, g for the selected draw, 0 for the others.
+                    // Column kc's loss term is counted here, once.
                     const bool qpre = pre && q == p;
                     const uint32_t kc = (qpre ? nx_a : e.uk[q]) - b0, bm = b1 - b0, nn = NP - 1u;
                     for (uint32_t s0 = 0; s0 < NP; s0 += (uint32_t)G) {
@@ -505,21 +509,19 @@ __global__ __launch_bounds__(SLK_EPOCH_TB) void k_bilinear_epoch(slk_epoch_args 
                             const uint32_t f = s == 0u ? 0u : kc * nn + (s - 1u);
                             const uint32_t col = s == 0u ? kc : f % bm, row = s == 0u ? 0u : f / bm;
                             const float sp = slk_ld_coh(e.sk + (size_t)(b0 + col) * NP);
-                            float best = 0.0f;
-                            uint32_t best_r = 0u;
-                            for (uint32_t r = 0; r < nn; ++r) {
-                                const uint32_t fr = r * bm + col;
-                                const float sc = slk_ld_coh(e.sk + (size_t)(b0 + fr / nn) * NP + 1u + fr % nn);
-                                if (r == 0u || sc > best) {
-                                    best = sc;
-                                    best_r = r;
-                                }
-                            }
-                            const float x = best - sp + 1.0f;
-                            const float g = x >= 0.0f ? inv_b : 0.0f;
+                            uint32_t best_r;
+                            float g_unit, l;
+                            slk_column_select(
+                                COLUMN_LOSS, e.n_items, sp, nn,
+                                [&](uint32_t r) {
+                                    const uint32_t fr = r * bm + col;
+                                    return slk_ld_coh(e.sk + (size_t)(b0 + fr / nn) * NP + 1u + fr % nn);
+                                },
+                                best_r, g_unit, l);
+                            const float g = slk_column_g(g_unit, inv_b);
                             if (s == 0u) {
                                 gs = -g;
-                                loss_acc_d += (double)(x > 0.0f ? x : 0.0f);
+                                loss_acc_d += (double)l;
                             } else {
                                 gs = best_r == row ? g : 0.0f;
                             }
@@ -718,10 +720,12 @@ template <int VEC, int G>
 static slk_epoch_fn epoch_fn(int upd, int mode) {
     if (mode == SLK_EMODE_EXPLICIT) return epoch_fn_of<VEC, G, SLK_EMODE_EXPLICIT>(upd);
     if (mode == SLK_EMODE_ADAPTIVE) return epoch_fn_of<VEC, G, SLK_EMODE_ADAPTIVE>(upd);
+    if (mode == SLK_EMODE_WARP) return epoch_fn_of<VEC, G, SLK_EMODE_WARP>(upd);
     return epoch_fn_of<VEC, G, SLK_EMODE_PAIR>(upd);
 }
 static int epoch_mode_of(int loss) {
-    return loss >= SLK_LOSS_REGRESSION ? SLK_EMODE_EXPLICIT : (loss == SLK_LOSS_ADAPTIVE_HINGE ? SLK_EMODE_ADAPTIVE : SLK_EMODE_PAIR);
+    if (slk_loss_is_explicit(loss)) return SLK_EMODE_EXPLICIT;
+    return loss == SLK_LOSS_WARP ? SLK_EMODE_WARP : (loss == SLK_LOSS_ADAPTIVE_HINGE ? SLK_EMODE_ADAPTIVE : SLK_EMODE_PAIR);
 }
 
 // Whether a slk_bilinear_train call takes the persistent route (option "epoch_kernel": 0 never, 1 when eligible).
@@ -730,7 +734,7 @@ bool slk_epoch_eligible(const slk_ctx *ctx, const slk_tables *tables, const slk_
     if (!ctx->opt_epoch_kernel || ctx->epoch_refused || bloom) return false;
     // one-negative pair losses, the explicit-feedback losses, adaptive hinge over ALL 1 + n occurrences (the chunk-sorted item
     // list; the launch path's per-minibatch live lists start at adaptive_late_min_batch, far above epoch_max_batch)
-    if (loss == SLK_LOSS_ADAPTIVE_HINGE &&
+    if (slk_loss_is_column(loss) &&
         (!ctx->opt_epoch_adaptive || bsz > ctx->opt_epoch_adaptive_max_batch || bsz >= ctx->opt_adaptive_late_min_batch))
         return false;
     if (bsz > ctx->opt_epoch_max_batch) return false;
@@ -818,7 +822,7 @@ int slk_epoch_run_chunk(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim
                         float *d_mb_loss, const float *d_ratings, hipStream_t s) {
     const int mode = epoch_mode_of(loss);
     const bool expl = mode == SLK_EMODE_EXPLICIT;  // d_ratings: the chunk's ratings, indexed by pb.uval[1] (see prep_sort)
-    const bool adp = mode == SLK_EMODE_ADAPTIVE;   // NP = 1 + negatives per interaction (pair losses 2, explicit 1)
+    const bool adp = mode == SLK_EMODE_ADAPTIVE || mode == SLK_EMODE_WARP;   // NP = 1 + negatives per interaction (pair losses 2, explicit 1)
     int vec, g, rc;
     if (!slk_pick_layout(tables->dim, &vec, &g)) return slk_fail(ctx, SLK_EINVAL, "embedding dim %d unsupported", tables->dim);
     const uint32_t n_mb = (uint32_t)((nc + bsz - 1) / bsz);

@@ -30,6 +30,7 @@ struct slk_foldin_args {
     int64_t n;
     int64_t wg_min;                 // histories of at least this many interactions are the workgroup route's
     uint32_t H;
+    uint32_t num_items;             // warp: the catalogue size of the rank estimate (slk_warp_weight)
     int D, nn, loss_kind, kind, nsteps;
     slk_opt_hyper hyper;
     slk_opt_coef c[SLK_FOLDIN_MAX_STEPS];
@@ -50,7 +51,10 @@ __device__ __forceinline__ void slk_foldin_step(const slk_foldin_args &a, const 
 // interactions at `pos` (negatives: neg[r * n + position]).  Every group of the unit makes the same number of trips (the
 // shuffles inside are then taken by whole waves); a group without a position in a trip loads nothing and adds nothing.
 // All row loads of a trip are issued before the first use, the ids of the next trip behind them.
-template <int VEC, int G, bool ADP, int NGRP>
+// ADP: 0 the pair losses (a.loss_kind), else the column loss this instantiation is compiled for (SLK_LOSS_ADAPTIVE_HINGE /
+// SLK_LOSS_WARP: a constant, so that adaptive hinge keeps its registers -- read from the arguments it cost the gfx950 build
+// 2-5 VGPRs and 2-13 spilled SGPRs)
+template <int VEC, int G, int ADP, int NGRP>
 __device__ __forceinline__ void slk_foldin_gather(const slk_foldin_args &a, const int64_t *pos, const int64_t *neg, int64_t m, int grp,
                                                   int d0, bool on, const slk_vec<VEC> &u, float bu, float inv_b, slk_vec<VEC> &gacc,
                                                   float &gb, double &lacc) {
@@ -104,8 +108,10 @@ __device__ __forceinline__ void slk_foldin_gather(const slk_foldin_args &a, cons
             }
         }
     } else {
-        // adaptive hinge (spotlight/losses.py:127-166 on a one-user minibatch): of the position's nn candidates the one with the
-        // largest score, the FIRST on ties (torch.max(dim=0), k_adaptive_select), and the hinge against it
+        // the column losses on a one-user minibatch (row r of column j is neg[r * n + j]).  Adaptive hinge (spotlight/losses.py:
+        // 127-166): of the position's nn candidates the one with the largest score, the FIRST on ties (torch.max(dim=0)), and
+        // the hinge against it.  Warp: the first candidate that violates the margin, latched (slk_column_feed), and the hinge
+        // against it scaled by the weight of its row; no violator adds nothing.  The rule is k_adaptive_select's.
         constexpr int NB = SLK_FOLDIN_NEG_BATCH;
         const int nn = a.nn;
         bool act = grp < m;
@@ -118,7 +124,11 @@ __device__ __forceinline__ void slk_foldin_gather(const slk_foldin_args &a, cons
             const bool actn = jn < m;
             const uint32_t ipn = actn ? (uint32_t)pos[jn] : 0u;
             slk_vec<VEC> vbest = slk_vzero<VEC>();
-            float best = 0.0f;
+            // the positive's score: warp's latch needs it ahead of the candidates; adaptive hinge forms it behind them, where it
+            // always has (a register held across the candidate loop cost k_foldin_wave<VEC 1> a wave of occupancy)
+            float sp = 0.0f;
+            if (ADP == SLK_LOSS_WARP) sp = slk_group_sum<G>(slk_vdot<VEC>(u, vi)) + bu + bip;
+            slk_column_pick pick = slk_column_begin();
             for (int r0 = 0; r0 < nn; r0 += NB) {
                 uint32_t in[NB];
                 bool ra[NB];
@@ -137,16 +147,14 @@ __device__ __forceinline__ void slk_foldin_gather(const slk_foldin_args &a, cons
 #pragma unroll
                 for (int e = 0; e < NB; ++e) {
                     const float sc = slk_group_sum<G>(slk_vdot<VEC>(u, vj[e])) + bu + bin[e];
-                    if (ra[e] && (r0 + e == 0 || sc > best)) {
-                        best = sc;
-                        vbest = vj[e];
-                    }
+                    if (ra[e] && slk_column_feed(ADP, pick, sp, (uint32_t)(r0 + e), sc)) vbest = vj[e];
                 }
             }
-            const float sp = slk_group_sum<G>(slk_vdot<VEC>(u, vi)) + bu + bip;
+            if (ADP != SLK_LOSS_WARP) sp = slk_group_sum<G>(slk_vdot<VEC>(u, vi)) + bu + bip;
             if (act) {
-                float l, gp, gn;
-                slk_pair_loss(SLK_LOSS_ADAPTIVE_HINGE, sp, best, inv_b, l, gp, gn);
+                float l, g_unit;
+                slk_column_finish(ADP, a.num_items, pick, sp, g_unit, l);
+                const float gn = slk_column_g(g_unit, inv_b), gp = -gn;
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) gacc.v[i] += gp * vi.v[i] + gn * vbest.v[i];
                 gb += gp + gn;
@@ -159,7 +167,7 @@ __device__ __forceinline__ void slk_foldin_gather(const slk_foldin_args &a, cons
 }
 
 // ---- wave route -----------------------------------------------------------------------------------------------------------------
-template <int VEC, int G, bool ADP>
+template <int VEC, int G, int ADP>
 __global__ __launch_bounds__(256) void k_foldin_wave(slk_foldin_args a) {
     constexpr int NG = 64 / G;
     const int lane64 = (int)(threadIdx.x & 63u);
@@ -222,7 +230,7 @@ __global__ __launch_bounds__(256) void k_foldin_wave(slk_foldin_args a) {
 }
 
 // ---- workgroup route ------------------------------------------------------------------------------------------------------------
-template <int VEC, int G, bool ADP>
+template <int VEC, int G, int ADP>
 __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
     constexpr int GPB = 256 / G;
     constexpr int DL = G * VEC;  // LDS row length (>= D)
@@ -317,15 +325,18 @@ __global__ __launch_bounds__(256) void k_foldin_wg(slk_foldin_args a) {
 
 typedef void (*slk_foldin_fn)(slk_foldin_args);
 
-static void foldin_pick(int vec, int g, bool adp, slk_foldin_fn *wave, slk_foldin_fn *wg) {
+static void foldin_pick(int vec, int g, int column_loss, slk_foldin_fn *wave, slk_foldin_fn *wg) {
 #define SLK_FOLDIN_PICK(V, GG)                                  \
     do {                                                        \
-        if (adp) {                                              \
-            *wave = k_foldin_wave<V, GG, true>;                 \
-            *wg = k_foldin_wg<V, GG, true>;                     \
+        if (column_loss == SLK_LOSS_WARP) {                     \
+            *wave = k_foldin_wave<V, GG, SLK_LOSS_WARP>;        \
+            *wg = k_foldin_wg<V, GG, SLK_LOSS_WARP>;            \
+        } else if (column_loss) {                               \
+            *wave = k_foldin_wave<V, GG, SLK_LOSS_ADAPTIVE_HINGE>; \
+            *wg = k_foldin_wg<V, GG, SLK_LOSS_ADAPTIVE_HINGE>;  \
         } else {                                                \
-            *wave = k_foldin_wave<V, GG, false>;                \
-            *wg = k_foldin_wg<V, GG, false>;                    \
+            *wave = k_foldin_wave<V, GG, 0>;                    \
+            *wg = k_foldin_wg<V, GG, 0>;                        \
         }                                                       \
     } while (0)
     SLK_FOR_LAYOUT(vec, g, SLK_FOLDIN_PICK);
@@ -340,11 +351,12 @@ SLK_EXPORT int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_o
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: n_steps %lld and n_new_users %lld must be at least 1", (long long)n_steps,
                         (long long)n_new_users);
     if (n < 0) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: n %lld is negative", (long long)n);
-    if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_ADAPTIVE_HINGE)
+    if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_WARP || slk_loss_is_explicit(loss))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: loss %d is not an implicit-feedback loss (explicit feedback needs ratings)",
                         loss);
-    if (loss == SLK_LOSS_ADAPTIVE_HINGE && n_neg < 1)
-        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: adaptive hinge needs n_neg >= 1 (got %d)", n_neg);
+    const bool column = slk_loss_is_column(loss);
+    if (column && n_neg < 1)
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: %s needs n_neg >= 1 (got %d)", slk_column_loss_name(loss), n_neg);
     if (!d_off || (n > 0 && (!d_items || !d_neg)))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: the histories (d_off / d_items) or the negatives (d_neg) are NULL");
     if (tables && (tables->user_bloom || tables->item_bloom))
@@ -359,9 +371,9 @@ SLK_EXPORT int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_o
     slk_call call(ctx, stream);
     if ((rc = call.begin(SLK_K_USER_PASS))) return rc;
 
-    const int nn = loss == SLK_LOSS_ADAPTIVE_HINGE ? n_neg : 1;
+    const int nn = column ? n_neg : 1;
     slk_foldin_fn wave_fn = nullptr, wg_fn = nullptr;
-    foldin_pick(vec, g, loss == SLK_LOSS_ADAPTIVE_HINGE, &wave_fn, &wg_fn);
+    foldin_pick(vec, g, column ? (int)loss : 0, &wave_fn, &wg_fn);
     slk_foldin_args a;
     memset(&a, 0, sizeof(a));
     a.U = tables->d_param[0];
@@ -376,6 +388,7 @@ SLK_EXPORT int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_o
     a.items = d_items;
     a.n = n;
     a.H = (uint32_t)n_new_users;
+    a.num_items = (uint32_t)tables->num_items;
     a.D = tables->dim;
     a.nn = nn;
     a.loss_kind = loss;

@@ -1024,7 +1024,77 @@ static __global__ __launch_bounds__(256) void k_item_multi_flags(const uint32_t 
 }
 
 // ---------------------------------------------------------------------------------------
-// adaptive hinge: the per-column selection of _get_multiple_negative_predictions' view(n, B) layout
+// The column losses (adaptive hinge, warp): ONE column's selection, written once for every route -- k_adaptive_select (the
+// staged route, the weighted route, the late live list, the row-sharded path), the persistent kernel's user phase
+// (slk_epoch.hip) and the fold-in gather (slk_foldin.hip).
+//   adaptive hinge  the largest candidate, the FIRST on ties (torch.max(dim=0)); l = max(x, 0), dL/dscore = 1/B where x >= 0
+//                   (clamp's backward is inclusive at 0), x = s_best - sp + 1
+//   warp            the FIRST candidate r with x_r = s_r - sp + 1 > 0 (strict; a NaN does not violate), the hinge scaled by
+//                   slk_warp_weight(I, r); no violator: l = 0 and no gradient (include/spotlight_hip.h, SLK_LOSS_WARP)
+// ---------------------------------------------------------------------------------------
+// warp's weight from the number of tries t + 1 it took to find the violator: log of LightFM's rank estimate floor((I-1) / tries)
+__device__ __forceinline__ float slk_warp_weight(uint32_t num_items, uint32_t t) {
+    return logf(fmaxf(1.0f, (float)((num_items - 1u) / (t + 1u))));
+}
+
+struct slk_column_pick {
+    float s;       // the score of the candidate selected so far
+    uint32_t row;  // its row r of the [n, B] candidate matrix
+    bool hit;      // warp: a violator has been latched (adaptive hinge: unused)
+};
+
+__device__ __forceinline__ slk_column_pick slk_column_begin() { return {0.0f, 0u, false}; }
+
+// Candidate r (fed in row order) with score sc against the positive's score sp; returns whether it is the selection now.
+__device__ __forceinline__ bool slk_column_feed(int loss_kind, slk_column_pick &k, float sp, uint32_t r, float sc) {
+    bool take;
+    if (loss_kind == SLK_LOSS_WARP) {
+        take = !k.hit && sc - sp + 1.0f > 0.0f;
+        k.hit = k.hit || take;
+    } else {
+        take = r == 0u || sc > k.s;  // torch.max(dim=0): first maximum wins ties
+    }
+    if (take) {
+        k.s = sc;
+        k.row = r;
+    }
+    return take;
+}
+
+// The column's loss term l and the magnitude of dL/dscore WITHOUT its 1 / B (adaptive hinge: 0 or 1; warp: 0 or the weight):
+// -g on the positive and +g on row k.row, g = slk_column_g(...); g_unit == 0 means that nothing of the column is live.
+__device__ __forceinline__ void slk_column_finish(int loss_kind, uint32_t num_items, const slk_column_pick &k, float sp,
+                                                  float &g_unit, float &l) {
+    const float x = k.s - sp + 1.0f;
+    if (loss_kind == SLK_LOSS_WARP) {
+        const float om = k.hit ? slk_warp_weight(num_items, k.row) : 0.0f;
+        g_unit = om;
+        l = k.hit ? om * x : 0.0f;
+    } else {
+        g_unit = x >= 0.0f ? 1.0f : 0.0f;
+        l = x > 0.0f ? x : 0.0f;
+    }
+}
+
+// |dL/dscore| of a column from g_unit: times 1 / B -- or, with interaction weights, times the weight of the column's
+// positive over the minibatch's weight sum (slk_weight_scale).  1.0f * inv_b is inv_b: adaptive hinge keeps its bits.
+__device__ __forceinline__ float slk_column_g(float g_unit, float inv_b) { return g_unit != 0.0f ? g_unit * inv_b : 0.0f; }
+__device__ __forceinline__ float slk_column_g_weighted(float g_unit, float w, float inv_W) {
+    return g_unit != 0.0f ? slk_weight_scale(g_unit, w, inv_W) : 0.0f;
+}
+
+// A whole column whose candidate scores are there to be read: score_of(r) = s_r.  Gives the selected row, g_unit and l.
+template <class SCORE_OF>
+__device__ __forceinline__ void slk_column_select(int loss_kind, uint32_t num_items, float sp, uint32_t nn, SCORE_OF score_of,
+                                                  uint32_t &row, float &g_unit, float &l) {
+    slk_column_pick k = slk_column_begin();
+    for (uint32_t r = 0; r < nn; ++r) slk_column_feed(loss_kind, k, sp, r, score_of(r));
+    slk_column_finish(loss_kind, num_items, k, sp, g_unit, l);
+    row = k.row;
+}
+
+// ---------------------------------------------------------------------------------------
+// the per-column selection of _get_multiple_negative_predictions' view(n, B) layout
 // (factorization/implicit.py:266-275) over the scores of every (interaction, pair).  A template only so that the one
 // definition serves slk_bilinear.hip and slk_shard.hip (no relocatable device code in this build).
 // ---------------------------------------------------------------------------------------
@@ -1038,7 +1108,7 @@ template <int UNUSED>
 __global__ __launch_bounds__(256) void k_adaptive_select(const float *sk, float *gk, uint32_t k0, uint32_t bm,
                                                          int nn, float inv_b, double *loss_partial,
                                                          const uint32_t *qk, uint32_t *live, const float *w,
-                                                         const double *wsum) {
+                                                         const double *wsum, int loss_kind, uint32_t num_items) {
     __shared__ double red[256];
     const int NP = nn + 1;
     double lsum = 0.0;
@@ -1047,21 +1117,18 @@ __global__ __launch_bounds__(256) void k_adaptive_select(const float *sk, float 
     const float inv_W = w ? 1.0f / (float)*wsum : 0.0f;
     for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < bm; c += gridDim.x * 256) {
         const float sp = sk[(size_t)(k0 + c) * NP];
-        float best = 0.0f;
-        size_t best_at = 0;
-        for (int r = 0; r < nn; ++r) {
-            const uint32_t f = (uint32_t)r * bm + c;  // flat index into the n*B draws
-            const size_t at = (size_t)(k0 + f / (uint32_t)nn) * NP + 1 + (f % (uint32_t)nn);
-            const float sc = sk[at];
-            if (r == 0 || sc > best) {  // torch.max(dim=0): first maximum wins ties
-                best = sc;
-                best_at = at;
-            }
-        }
-        const float x = best - sp + 1.0f;
+        // row r of column c is flat draw f = r * bm + c of the n*B draws: pair 1 + f % n of interaction k0 + f / n
+        const auto at_of = [&](uint32_t r) {
+            const uint32_t f = r * bm + c;
+            return (size_t)(k0 + f / (uint32_t)nn) * NP + 1 + (f % (uint32_t)nn);
+        };
+        uint32_t best_r;
+        float g_unit, l;
+        slk_column_select(loss_kind, num_items, sp, (uint32_t)nn, [&](uint32_t r) { return sk[at_of(r)]; }, best_r, g_unit, l);
+        const size_t best_at = at_of(best_r);
         const float wc = w ? w[k0 + c] : 1.0f;
-        lsum += w ? (double)wc * (double)(x > 0.0f ? x : 0.0f) : (double)(x > 0.0f ? x : 0.0f);
-        const float g = x >= 0.0f ? (w ? slk_weight_scale(1.0f, wc, inv_W) : inv_b) : 0.0f;
+        lsum += w ? (double)wc * (double)l : (double)l;
+        const float g = w ? slk_column_g_weighted(g_unit, wc, inv_W) : slk_column_g(g_unit, inv_b);
         gk[(size_t)(k0 + c) * NP] = -g;
         // the column's n draws are written by this thread alone, and the columns partition the n*B draws: every entry of
         // gk gets its value here (no memset before the launch)

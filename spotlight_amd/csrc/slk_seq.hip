@@ -614,6 +614,8 @@ static int poolnet_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim 
     if (n_seq < 0 || batch_size < 1 || seq_len < 1)
         return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: n_seq %lld batch_size %lld seq_len %lld", (long long)n_seq,
                         (long long)batch_size, (long long)seq_len);
+    if (loss == SLK_LOSS_WARP)
+        return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: warp (loss kind %d) is not built for the sequence model", loss);
     if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_ADAPTIVE_HINGE)
         return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", loss);
     const bool adaptive = loss == SLK_LOSS_ADAPTIVE_HINGE;

@@ -714,6 +714,8 @@ SLK_EXPORT int slk_shard_user_pass(slk_ctx *ctx, const slk_tables *local, const 
                                    const float *d_rows_in, float *d_grad_out, float *d_loss_out, int32_t accumulate,
                                    void *stream) {
     if (!ctx) return SLK_EINVAL;
+    if (loss == SLK_LOSS_WARP)  // (answered first: whatever else the call holds, this path has no warp selection)
+        return slk_fail(ctx, SLK_EINVAL, "slk_shard_user_pass: warp (loss kind %d) is not built on the row-sharded path", loss);
     int vec, g, rc;
     if ((rc = slk_check_tables(ctx, local, 15u, &vec, &g, /*shadow_ok=*/true))) return rc;
     if ((rc = check_plain(ctx, local))) return rc;
@@ -848,7 +850,7 @@ SLK_EXPORT int slk_shard_adaptive_select(slk_ctx *ctx, int64_t global_batch, int
     slk_prof_begin(ctx, SLK_K_SCORE, s);
     hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, d_scores, d_gk, 0u, (uint32_t)global_batch, (int)n_neg,
                        inv_b, (double *)ctx->losspart.p, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const float *)nullptr,
-                       (const double *)nullptr);  // (no interaction weights on the row-sharded path)
+                       (const double *)nullptr, (int)SLK_LOSS_ADAPTIVE_HINGE, 0u);  // (no interaction weights, no warp on the row-sharded path)
     SLK_LAUNCH_CHECK(ctx, "k_adaptive_select");
     slk_prof_end(ctx, s);
     // every rank has computed the whole minibatch's loss; the ranks' shares must ADD UP to it: one rank reports it

@@ -36,6 +36,9 @@ _BIAS_SHADOW_MIN_ITEMS = 1 << 24
 # copy that does not hold the current one and no pre-step-row record (a row per interaction: 13 % of the pass's traffic), the item
 # pass gathers the pre-step row where it still stands.  Below, the passes are latency-bound and the record is cache-resident.
 _USER_PINGPONG_MIN_BATCH = 1 << 17
+# The column losses: num_negative_samples draws per positive, viewed as [n, B] (implicit.py:266-275), one selection per column --
+# adaptive hinge the largest candidate, warp the first violating one (include/spotlight_hip.h: SLK_LOSS_WARP)
+COLUMN_LOSSES = ('adaptive_hinge', 'warp')
 
 
 def _engine_for(device):
@@ -336,6 +339,12 @@ class ImplicitFactorizationModel(object):
       negatives exactly as the reference draws them, the embedding gathers and their backward through this package's
       kernels when the module is built from this package's layers.  Slower than the fused path by the reference's own
       per-minibatch overheads, never on the CPU.
+    * `loss='warp'` (not in the reference): the rank-weighted hinge of WSABIE / LightFM's `loss='warp'`.  Of a positive's
+      `num_negative_samples` draws -- adaptive hinge's, in its `view(n, B)` layout, all drawn and scored up front -- the FIRST one
+      that violates the margin (`neg - pos + 1 > 0`) is trained against, the hinge scaled by `log(max(1, (num_items - 1) // tries))`;
+      a positive without a violator contributes nothing.  The RandomState is consumed exactly as by `loss='adaptive_hinge'` with
+      the same `num_negative_samples`.  The rank estimate assumes uniform draws: under `negative_sampling='popularity'` it is a
+      popularity-weighted rank (include/spotlight_hip.h: SLK_LOSS_WARP; `spotlight_amd.losses.warp_loss` on the autograd route).
     * `negative_sampling` (not in the reference): what the negatives are drawn from.  'uniform' or None: every item alike
       (`RandomState.randint`, the reference's sampler).  'popularity': in proportion to
       `count(item) ** negative_sampling_power` (word2vec's unigram distribution; default power 0.75), the counts taken over
@@ -360,7 +369,7 @@ class ImplicitFactorizationModel(object):
                  sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
                  negative_sampling_power=0.75, use_weights=False):
 
-        assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge')
+        assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge', 'warp')
         _sampling.check_negative_sampling(negative_sampling)
 
         self._loss = loss
@@ -484,7 +493,7 @@ class ImplicitFactorizationModel(object):
             self._initialize(interactions)
 
         n = len(user_ids)
-        nn = self._num_negative_samples if self._loss == 'adaptive_hinge' else 1
+        nn = self._num_negative_samples if self._loss in COLUMN_LOSSES else 1
         autograd = getattr(self, '_autograd_route', False)
         # non-uniform negatives are handed in at every size (the two-lane schedule): the three-stage pipeline's
         # slk_bilinear_prefetch draws uniform ones ahead of time
@@ -552,7 +561,8 @@ class ImplicitFactorizationModel(object):
         from spotlight_amd.sampling import sample_items
         from spotlight_amd.torch_utils import minibatch, shuffle
         loss_func = {'pointwise': _losses.pointwise_loss, 'bpr': _losses.bpr_loss, 'hinge': _losses.hinge_loss,
-                     'adaptive_hinge': _losses.adaptive_hinge_loss}[self._loss]
+                     'adaptive_hinge': _losses.adaptive_hinge_loss,
+                     'warp': lambda pos, neg, **kw: _losses.warp_loss(pos, neg, self._num_items, **kw)}[self._loss]
         device = next(self._net.parameters()).device
         self._net.train(True)
 
@@ -569,7 +579,7 @@ class ImplicitFactorizationModel(object):
             for batch in minibatch(*tensors, batch_size=self._batch_size):
                 batch_user, batch_item = batch[:2]
                 positive_prediction = self._net(batch_user, batch_item)
-                if self._loss == 'adaptive_hinge':
+                if self._loss in COLUMN_LOSSES:
                     # implicit.py:266-275: users repeated user-major, ONE draw of B * n, scores viewed as [n, B]
                     n = self._num_negative_samples
                     batch_size = batch_user.size(0)

@@ -333,7 +333,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
     torch's CPU generator in the reference's order and this rank keeps rows `rank::world`.
 
     All four losses (adaptive hinge: a score phase and a selection over the whole minibatch in front of the user pass,
-    ShardedBilinearTrainer.run_chunk).  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
+    ShardedBilinearTrainer.run_chunk); loss='warp' is not built here and raises NotImplementedError at construction, before
+    anything is drawn.  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
     sharded yet: use_weights=True raises ValueError at construction.
 
     Evaluation runs shard by shard as well: evaluation.mrr_score (_fused_ranks), precision_recall_score (_batch_scores) and
@@ -343,6 +344,9 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
 
     def __init__(self, *args, **kwargs):
         self._group = kwargs.pop('group', None)
+        # (before the base constructor: it draws the model's seed from random_state)
+        if kwargs.get('loss', args[0] if args else 'pointwise') == 'warp':
+            raise NotImplementedError("loss='warp': warp is not built on the row-sharded path")
         super(ShardedImplicitFactorizationModel, self).__init__(*args, **kwargs)
         if self._use_weights:
             raise ValueError('use_weights=True is not supported by the row-sharded path: interaction weights are not sharded yet')

@@ -117,7 +117,8 @@ def generic_steps(model, table, bias, off, items, neg, emb, b, T):
     history; a user without one keeps theirs untouched, whatever the optimizer does to a zero gradient)."""
     from spotlight_amd import losses as _losses
     loss_func = {'pointwise': _losses.pointwise_loss, 'bpr': _losses.bpr_loss, 'hinge': _losses.hinge_loss,
-                 'adaptive_hinge': _losses.adaptive_hinge_loss}[model._loss]
+                 'adaptive_hinge': _losses.adaptive_hinge_loss,
+                 'warp': lambda pos, neg: _losses.warp_loss(pos, neg, model._num_items)}[model._loss]
     device = table.device
     lens = np.diff(off)
     live = np.nonzero(lens > 0)[0]
@@ -129,8 +130,8 @@ def generic_steps(model, table, bias, off, items, neg, emb, b, T):
     row_of = torch.from_numpy(np.repeat(np.arange(live.size), lens[live])).to(device)
     d_items = torch.from_numpy(items).to(device)
     bounds = np.concatenate([[0], np.cumsum(lens[live])])
-    adaptive = model._loss == 'adaptive_hinge'
-    score = lambda ids: (u[row_of] * table[ids]).sum(1) + ub[row_of] + bias[ids]
+    adaptive = model._loss in _host.COLUMN_LOSSES  # every candidate row of the column goes to the loss
+    score =lambda ids: (u[row_of] * table[ids]).sum(1) + ub[row_of] + bias[ids]
     for t in range(T):
         opt.zero_grad()
         pos = score(d_items)
@@ -159,7 +160,7 @@ def fold_in(model, interactions, n_iter=None, init=None, negatives=None, generic
     if T < 1:
         raise ValueError('n_iter must be at least 1, got {!r}'.format(n_iter))
     dim = int(table.shape[1])
-    nn = model._num_negative_samples if model._loss == 'adaptive_hinge' else 1
+    nn = model._num_negative_samples if model._loss in _host.COLUMN_LOSSES else 1
     if H < 1:
         return np.zeros((0, dim), np.float32), np.zeros(0, np.float32)
     device = table.device

@@ -49,6 +49,32 @@ def adaptive_hinge_loss(positive_predictions, negative_predictions, mask=None, w
     return hinge_loss(positive_predictions, hardest.squeeze(), mask=mask, weights=weights)
 
 
+def warp_loss(positive_predictions, negative_predictions, num_items, mask=None, weights=None):
+    """WARP (WSABIE; LightFM's loss='warp'; not in the reference): the hinge against the FIRST of the sampled negatives
+    that violates the margin, scaled by a weight from how many tries it took.  negative_predictions has the candidates
+    along dim 0, in draw order, as for adaptive_hinge_loss.  Per column, with x_r = neg_r - pos + 1:
+
+        t = the smallest r with x_r > 0 (strict; a NaN does not violate); none: the column's term is 0, no gradient
+        w = log(max(1, (num_items - 1) // (t + 1)))         -- LightFM's rank estimate floor((I - 1) / tries)
+        l = w * x_t
+
+    The weight is a constant of the backward pass: d l / d pos = -w, d l / d neg_t = +w, every other candidate 0.
+    All candidates are scored (no early stop).  The estimate assumes uniform draws; under
+    negative_sampling='popularity' it is a popularity-weighted rank   (include/spotlight_hip.h: SLK_LOSS_WARP)."""
+    x = negative_predictions - positive_predictions.unsqueeze(0) + 1.0
+    viol = x > 0
+    n = x.shape[0]
+    rows = torch.arange(n, device=x.device).view((n,) + (1,) * (x.dim() - 1)).expand_as(x)
+    first = torch.where(viol, rows, torch.full_like(rows, n)).min(0)[0]
+    hit = first < n
+    t = first.clamp(max=n - 1)
+    rank = torch.div(torch.full_like(t, int(num_items) - 1), t + 1, rounding_mode='floor').clamp(min=1)
+    w = torch.log(rank.to(x.dtype))  # fp32 predictions: logf of the fp32 rank, as the kernels form it
+    x_t = x.gather(0, t.unsqueeze(0)).squeeze(0)
+    terms = torch.where(hit, w * x_t, torch.zeros_like(x_t))
+    return _masked_mean(terms, mask, weights)
+
+
 def regression_loss(observed_ratings, predicted_ratings, weights=None):
     """Mean squared error   (losses.py:169-191)."""
     assert_no_grad(observed_ratings)

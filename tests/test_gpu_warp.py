@@ -1,0 +1,119 @@
+"""loss='warp' (SLK_LOSS_WARP) on the real gfx950 library: the checks of tests/warp_checks.py that tests/test_emu_warp.py runs on
+the emulator build, and the model-level cases of tests/test_host_warp.py on the device."""
+import pytest
+
+import warp_checks as wk
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def be():
+    from hip_backend import HipBackend
+    b = HipBackend()
+    yield b
+    b.close()
+
+
+@pytest.mark.parametrize('route', wk.ROUTES)
+@pytest.mark.parametrize('kind,D,n,I', wk.CLOSED)
+def test_closed_loop_matches_the_float64_restatement(be, kind, D, n, I, route):
+    wk.check_closed_loop(be, kind, D, n, I, route)
+
+
+@pytest.mark.parametrize('kind', wk.KINDS)
+def test_weighted_closed_loop_matches_the_float64_restatement(be, kind):
+    wk.check_closed_loop(be, kind, 24, 3, 333, 'launch', weights='case')
+
+
+@pytest.mark.parametrize('kind', wk.KINDS)
+def test_persistent_route_is_the_launch_path_bit_for_bit(be, kind):
+    for D, n in zip(wk.DS, (5, 3, 1, 5)):
+        wk.check_routes_agree(be, kind, D, n)
+    wk.check_routes_agree(be, kind, 24, 5, I=7)
+
+
+@pytest.mark.parametrize('weights', [None, 'case'])
+def test_chunking_is_bit_neutral_and_the_call_deterministic(be, weights):
+    wk.check_chunking_and_determinism(be, weights)
+
+
+def test_inside_the_training_scopes(be):
+    wk.check_scopes(be)
+
+
+@pytest.mark.parametrize('kind', wk.KINDS)
+def test_all_ones_is_the_unweighted_staged_call(be, kind):
+    wk.check_all_ones_is_the_unweighted_staged_call(be, kind)
+
+
+def test_a_power_of_two_on_every_weight_changes_no_bit(be):
+    wk.check_power_of_two_scaling(be)
+
+
+@pytest.mark.parametrize('route', wk.ROUTES)
+@pytest.mark.parametrize('how', ['two_items', 'no_violator'])
+@pytest.mark.parametrize('kind', wk.SPARSE)
+def test_a_step_without_a_live_column_changes_no_bit(be, kind, how, route):
+    wk.check_nothing_is_live(be, kind, route, how)
+
+
+@pytest.mark.parametrize('route', wk.ROUTES)
+def test_every_column_violating_at_row_zero(be, route):
+    wk.check_every_column_violates_at_row_zero(be, route)
+
+
+@pytest.mark.parametrize('route', wk.ROUTES)
+def test_a_nan_candidate_is_skipped(be, route):
+    wk.check_nan_candidate_is_skipped(be, route)
+
+
+@pytest.mark.parametrize('opt', wk.KINDS)
+def test_fold_in_closed_loop(be, opt):
+    for D, I, H, n in wk.FOLD_CLOSED + [wk.FOLD_CLOSED_7[wk.KINDS.index(opt) % 4]]:
+        wk.check_fold_closed_loop(be, opt, D, I, H, n)
+
+
+@pytest.mark.parametrize('D', wk.DS)
+def test_fold_in_batch_and_step_composition(be, D):
+    for I, n in ((333, 3), (7, 5)):
+        wk.check_fold_batch_composition(be, 'adagrad', D, I, n)
+        wk.check_fold_step_composition(be, 'adam_dense', D, I, n)
+
+
+def test_fold_in_item_side_is_frozen(be):
+    wk.check_fold_frozen(be, 'sparse_adam')
+
+
+def test_fold_in_degenerate_columns(be):
+    wk.check_fold_degenerate(be)
+
+
+def test_refusals_through_the_c_abi(be):
+    wk.check_refusals(be)
+
+
+# ---- model level, on the device: the bodies of tests/test_host_warp.py (their emulator fixture only points the models' device hooks
+# at the emulator; here the hooks stay the real ones)
+@pytest.mark.parametrize('kw', [{}, dict(use_weights=True), dict(negative_sampling='popularity')],
+                         ids=lambda kw: '+'.join(sorted(kw)) or 'plain')
+def test_fit_trains_and_consumes_the_random_state_as_adaptive_hinge_does(kw):
+    import test_host_warp as hw
+    hw.test_fit_trains_and_consumes_the_random_state_as_adaptive_hinge_does(None, kw)
+
+
+def test_one_minibatch_matches_warp_loss_through_autograd():
+    import test_host_warp as hw
+    hw.test_one_minibatch_matches_warp_loss_through_autograd(None)
+
+
+def test_generic_routes_train_through_warp_loss():
+    import test_host_warp as hw
+    hw.test_custom_representation_and_unfused_optimizer_train_through_warp_loss(None)
+
+
+@pytest.mark.parametrize('kind', ['adagrad', 'sgd'])
+def test_fused_fold_in_equals_the_generic_route(kind):
+    import test_host_warp as hw
+    hw.test_fused_fold_in_equals_the_generic_route(None, kind)
+    hw.test_fold_in_draws_num_negative_samples_per_position(None)
