@@ -297,6 +297,35 @@ int slk_cdf_guide(slk_ctx *ctx, const double *d_cdf, int64_t num_items, int32_t 
 int slk_sample_items_weighted(slk_ctx *ctx, const double *d_cdf, const uint32_t *d_guide, int32_t guide_bits, int64_t num_items,
                               int64_t count, int64_t *d_out, void *stream);
 
+/* Verified negatives (added to ABI 14: one new entry, nothing existing changes, SLK_ABI_VERSION stays): a sampled "negative"
+ * that the user has interacted with is replaced by the next of `tries` candidates that were all drawn up front.
+ *   the draw       for a minibatch of bm positives, T * nn * bm candidates in ONE draw (randint, or choice), laid out as the
+ *                  reference's view(rows, bm) with rows = T * nn (T = tries, nn = n_neg: 1 for pointwise / bpr / hinge, the
+ *                  number of negatives per positive for adaptive hinge / warp): candidate (a, r, c) -- attempt a, negative
+ *                  row r, column c -- is flat element (a * nn + r) * bm + c of the minibatch's block
+ *   block offsets  the blocks of successive minibatches follow each other in one contiguous draw: the candidate block of the
+ *                  minibatch that starts at interaction m_start starts at m_start * nn * T of d_cand, its output block at
+ *                  m_start * nn of d_neg_out; the last minibatch may be short
+ *   the selection  output (r, c) = cand[a*, r, c], a* the smallest a whose cand[a, r, c] is not in seen(user[c]); if all T
+ *                  attempts are seen, cand[0, r, c] -- the draw an unverified call would have used -- and the slot counts
+ *                  as unresolved
+ *   the output     per minibatch an (nn, bm) block: d_neg_out is what every training entry takes as d_neg_in
+ *   the stream     nothing is drawn here and no draw depends on data: the caller's draws stay numpy-exact, the RandomState
+ *                  ends where sample_items(num_items, (T * nn, bm)) per minibatch leaves it.  T = 1 copies d_cand
+ *   d_counts       NULL, or int64[2] to which the call ADDS the number of slots with a* > 0 (replaced) and the number of
+ *                  unresolved slots (the caller zeroes it)
+ *   seen           a CSR over users: int64 offsets d_seen_off[num_users + 1] and int64 items d_seen_items, ascending inside a
+ *                  user's segment; duplicates are allowed, segments may be empty.  The caller owns both arrays and their
+ *                  contents are its responsibility, as ids are; a user id outside [0, num_users) has an empty history and a
+ *                  segment is cut to [0, d_seen_off[num_users]].  Garbage offsets give wrong answers, never a kernel that
+ *                  does not end: at most `tries` attempts of at most 64 halvings each
+ * One thread per output slot, a binary search per attempt.  No scratch, no host wait; profiled under SLK_K_SAMPLE.
+ * n == 0 does nothing.  Refused with SLK_EINVAL: a NULL d_users / d_cand / d_seen_off / d_seen_items / d_neg_out with n > 0,
+ * tries outside [1, 16], n_neg < 1, batch_size < 1, n < 0, num_users < 0, d_neg_out overlapping d_cand. */
+int slk_verify_negatives(slk_ctx *ctx, const int64_t *d_users, int64_t n, int64_t batch_size, int32_t n_neg, int32_t tries,
+                         const int64_t *d_cand, const int64_t *d_seen_off, const int64_t *d_seen_items, int64_t num_users,
+                         int64_t *d_neg_out, int64_t *d_counts /* NULL: not counted */, void *stream);
+
 /* The minibatch loop of one epoch of ImplicitFactorizationModel.fit() after the shuffle
  * (factorization/implicit.py:223-243): contiguous minibatches of `batch_size` over the n
  * (user, item) pairs (short last batch); per minibatch: negatives (drawn from the ctx RNG

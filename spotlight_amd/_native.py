@@ -69,6 +69,8 @@ _PROTOTYPES = {
     'slk_cdf_guide': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     'slk_sample_items_weighted': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                             C.c_void_p]),
+    'slk_verify_negatives': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'slk_bilinear_train': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p,
                                      C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -373,6 +375,15 @@ class Engine(object):
         d_guide its cutpoint table (cdf_guide)."""
         self._check(self._lib.slk_sample_items_weighted(self._ctx, d_cdf, d_guide, int(guide_bits), int(num_items), int(count),
                                                         d_out, stream))
+
+    def verify_negatives(self, d_users, n, batch_size, n_neg, tries, d_cand, d_seen_off, d_seen_items, num_users, d_neg_out,
+                         d_counts=None, stream=0):
+        """include/spotlight_hip.h: slk_verify_negatives -- per negative slot the first of its `tries` candidates (d_cand: per
+        minibatch a [tries][n_neg][bm] block) that is not in the user's segment of the CSR (d_seen_off, d_seen_items), to
+        d_neg_out (per minibatch [n_neg][bm]: a training entry's d_neg_in); d_counts: None, or int64[2] to which the numbers of
+        replaced and of unresolved slots are added."""
+        self._check(self._lib.slk_verify_negatives(self._ctx, d_users, int(n), int(batch_size), int(n_neg), int(tries), d_cand,
+                                                   d_seen_off, d_seen_items, int(num_users), d_neg_out, d_counts, stream))
 
     # -- training / prediction ---------------------------------------------------------
     def bilinear_train(self, tables, optim, d_users, d_items, n, batch_size, loss, n_neg,

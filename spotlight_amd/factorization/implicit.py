@@ -25,6 +25,7 @@ _ENGINES = {}
 # at 10^8 interactions the two lanes time-slice the chip (train 71 ms + prepare 38 ms alone, 100 ms together:
 # profiles/r02_m_*_at_1e8_no_gain.json)
 _PIPELINE_MAX_DRAWS = 1 << 22
+_VERIFY_MAX_CANDIDATES = 1 << 25  # verify_negatives=True: candidates one draw covers at the most (a 256-MB scratch buffer)
 _DEFERRED_CHECK_MIN = 1 << 22  # ids per fit() from which the id-range checks run on worker threads beside the upload
 _PREFETCH = True  # large epochs: the next epoch's first chunk is prepared beside the last passes of this one (test switch)
 # Item tables of at least this many rows train with their biases and the biases' Adagrad accumulator interleaved for the duration
@@ -268,6 +269,31 @@ class _ImplicitEpochs(object):
         self.call = (n, model._batch_size, model._loss, model._num_negative_samples)
         self.mb_loss = torch.empty((n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
         self.slots, self.scopes, self.sources, self.weighted, self.side = [], [], None, False, None
+        self.seen = self.d_cand = self.d_counts = None  # verified negatives (verify_with)
+        self.tries, self.nn = 1, 1
+
+    def verify_with(self, seen, tries, nn):
+        """Two-lane schedule, verify_negatives=True: every epoch's negatives are the first unseen of `tries` candidates
+        (slk_verify_negatives against the bound SeenItems `seen`).  The candidates of a group of minibatches are drawn into
+        one scratch buffer of at most _VERIFY_MAX_CANDIDATES values (a minibatch's block at the least); the counters are
+        summed on the device over the whole fit()."""
+        self.seen, self.tries, self.nn = seen, int(tries), int(nn)
+        bsz = self.call[1]
+        per_mb = bsz * self.nn * self.tries
+        self.group = max(1, _VERIFY_MAX_CANDIDATES // per_mb) * bsz  # interactions per draw: whole minibatches
+        self.d_cand = torch.empty(min(self.n, self.group) * self.nn * self.tries, dtype=torch.int64, device=self.device)
+        self.d_counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def _draw_verified(self, engine, stream, d_users, d_neg):
+        """The epoch's T-fold draw, group by group (consecutive draws are one draw: the ids do not depend on the grouping),
+        each followed on the same stream by the selection into the slot's negatives."""
+        seen = self.seen
+        for lo in range(0, self.n, self.group):
+            m = min(self.group, self.n - lo)
+            _sampling.draw_items(engine, self.num_items, m * self.nn * self.tries, self.d_cand.data_ptr(), stream, self.dist)
+            engine.verify_negatives(d_users.data_ptr() + 8 * lo, m, self.call[1], self.nn, self.tries, self.d_cand.data_ptr(),
+                                    seen.d_off.data_ptr(), seen.d_items.data_ptr(), seen.num_users,
+                                    d_neg.data_ptr() + 8 * lo * self.nn, self.d_counts.data_ptr(), stream=stream)
 
     def reserve(self, engine, stream):
         engine.bilinear_reserve(self.tables, self.binding.as_struct(), *self.call, stream=stream)
@@ -296,6 +322,8 @@ class _ImplicitEpochs(object):
         if self.weighted:  # (on the prep lane's stream: the state read-back behind the negatives covers the conversion)
             with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
                 slot[4].view(torch.int32).copy_(slot[3])
+        if self.seen is not None:
+            return self._draw_verified(engine, stream, slot[0], d_neg)
         # one randint (one choice) per minibatch == one contiguous draw over the epoch (sampling.py:34)
         _sampling.draw_items(engine, self.num_items, d_neg.numel(), d_neg.data_ptr(), stream, self.dist)
 
@@ -362,15 +390,31 @@ class ImplicitFactorizationModel(object):
       interactions.  Such a fit runs the two-lane schedule at every size and opens neither training scope (item-bias shadow,
       user-row ping-pong); dL/dscore is formed ahead of the user pass (include/spotlight_hip.h: slk_bilinear_train_weighted).
       fold_in() stays unweighted.
+    * `verify_negatives` (not in the reference; LightFM and implicit's `verify_negative_samples`): False (default) uses every
+      draw as it comes, as the reference does -- a "negative" may then be an item the user has interacted with.  True: per
+      negative slot `verify_tries` (an int in [1, 16], default 4; ValueError at construction otherwise) candidates are drawn
+      up front -- per minibatch ONE draw of verify_tries * nn * B values, so the RandomState ends where
+      `sample_items(num_items, (verify_tries * nn, B))` per minibatch leaves it -- and the first one that is not in the
+      user's history (the interactions of the fit() call in progress) is used; if all are seen, the first one, and the slot
+      counts as unresolved (include/spotlight_hip.h: slk_verify_negatives; `spotlight_amd.sampling.verify_negatives` is the
+      rule in numpy, which the autograd route applies).  verify_tries=1 trains exactly as verify_negatives=False does and
+      only counts.  Such a fit runs the two-lane schedule at every size and composes with every loss, `use_weights` and
+      `negative_sampling`.  Afterwards `negative_verification_` holds {'candidates': values drawn, 'replaced': slots that do
+      not use their first candidate, 'unresolved'}, summed over the epochs, and `_seen_items` the histories' CSR (on the
+      device until the next fit(); not pickled).  fold_in() stays unverified.
     """
 
     def __init__(self, loss='pointwise', embedding_dim=32, n_iter=10, batch_size=256, l2=0.0,
                  learning_rate=1e-2, optimizer_func=None, use_cuda=False, representation=None,
                  sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
-                 negative_sampling_power=0.75, use_weights=False):
+                 negative_sampling_power=0.75, use_weights=False, verify_negatives=False, verify_tries=4):
 
         assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge', 'warp')
         _sampling.check_negative_sampling(negative_sampling)
+        self._verify_tries = _sampling.check_verify_tries(verify_tries)
+        self._verify_negatives = bool(verify_negatives)
+        self._seen_items = None  # sampling.SeenItems of the last verifying fit()
+        self.negative_verification_ = None  # {'candidates', 'replaced', 'unresolved'} of the last verifying fit()
 
         self._loss = loss
         self._embedding_dim = embedding_dim
@@ -501,7 +545,10 @@ class ImplicitFactorizationModel(object):
         # interaction weights (use_weights=True; a model pickled before the keyword existed has none): validated with the item
         # weights, before anything is drawn.  They ride the two-lane schedule's shuffle at every size, too.
         iw = interaction_weights(getattr(self, '_use_weights', False), interactions)
-        small = weighted or iw is not None or (self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS)
+        # verified negatives (verify_negatives=True; absent from a model pickled before the keyword existed): the selection runs
+        # between the draw and the training call, so these negatives are handed in at every size as well
+        verifying = getattr(self, '_verify_negatives', False)
+        small = weighted or iw is not None or verifying or (self._n_iter > 1 and n * nn <= _PIPELINE_MAX_DRAWS)
         # the id-range checks (implicit.py:169-182): four reductions over the host arrays, 12 ms at 2^25 ids.  On the large-epoch
         # path they run on worker threads beside the id upload and the first epoch's shuffle; their verdict is collected before
         # the first training call is enqueued (nothing the caller can observe has changed by then: the RandomState is restored,
@@ -514,6 +561,10 @@ class ImplicitFactorizationModel(object):
         self._item_distribution = _sampling.item_distribution(getattr(self, '_negative_sampling', None),
                                                               getattr(self, '_negative_sampling_power', 0.75), self._num_items,
                                                               item_ids)
+        # ... and the histories of this fit() that a verifying one checks its negatives against
+        self._seen_items = (_sampling.SeenItems.from_interactions(user_ids, item_ids, self._num_users, self._num_items)
+                            if verifying else None)
+        self.negative_verification_ = None
         if autograd:
             return self._fit_autograd(user_ids, item_ids, verbose, iw)
         binding = self._bind()
@@ -537,7 +588,14 @@ class ImplicitFactorizationModel(object):
         if small:
             sources = IdUpload([user_ids, item_ids], device).result()
             job.own_slots(sources + ([float_carrier(iw, device)] if iw is not None else []), nn, lane_stream=lane[1])
-            return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
+            if not verifying:
+                return _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
+            job.verify_with(self._seen_items.bind(engine, device, stream, ids=sources[:2]), self._verify_tries, nn)
+            _epochs.run_two_lane(engine, stream, lane, self._random_state, self._n_iter, verbose, job, device)
+            # the counters, summed on the device over the epochs and read back once (no epoch: the schedule still prepared one)
+            epochs = max(self._n_iter, 0)
+            self._store_verification(epochs * n * nn, *(job.d_counts.cpu().tolist() if epochs else (0, 0)))
+            return
         threaded = _PREFETCH and lane[0] is not engine and engine._lib is _native._LIB  # (the test harness's emulator is single-threaded)
         ids = _epochs.ShuffledIds(lane[0], lane[1], user_ids, item_ids, min(self._n_iter, 3 if _PREFETCH else 2), device)
         job.slots = ids.bufs
@@ -551,6 +609,12 @@ class ImplicitFactorizationModel(object):
                                           and not tables.user_bloom and not tables.item_bloom))]
         return _epochs.run_three_stage(engine, stream, self._random_state, self._n_iter, verbose, job, ids, check,
                                        prefetch=_PREFETCH, threaded=threaded)
+
+    def _store_verification(self, slots, replaced, unresolved):
+        """negative_verification_ of a verifying fit(): `slots` negatives were used, each the first unseen of verify_tries
+        candidates; `replaced` of them are not the first candidate, `unresolved` had every candidate seen (and use the first)."""
+        self.negative_verification_ = {'candidates': int(slots) * self._verify_tries, 'replaced': int(replaced),
+                                       'unresolved': int(unresolved)}
 
     def _fit_autograd(self, user_ids, item_ids, verbose, weights=None):
         """The reference's epoch / minibatch loop (implicit.py:208-252, 254-275) for models without a fused path: host numpy
@@ -566,9 +630,21 @@ class ImplicitFactorizationModel(object):
         device = next(self._net.parameters()).device
         self._net.train(True)
 
+        seen = getattr(self, '_seen_items', None)  # verify_negatives=True: the numpy restatement of slk_verify_negatives
+        counts = [0, 0, 0]  # slots, replaced, unresolved
+
         def negatives_for(batch_user, n_draws):
-            return torch.from_numpy(sample_items(self._num_items, n_draws, random_state=self._random_state,
-                                                 p=self._item_distribution)).to(device)
+            if seen is None:
+                return torch.from_numpy(sample_items(self._num_items, n_draws, random_state=self._random_state,
+                                                     p=self._item_distribution)).to(device)
+            # ONE draw of verify_tries * n_draws candidates, viewed [tries][n_draws / B][B]
+            cand = sample_items(self._num_items, self._verify_tries * n_draws, random_state=self._random_state,
+                                p=self._item_distribution)
+            picked, replaced, unresolved = _sampling.verify_negatives(cand, batch_user.cpu().numpy(), seen,
+                                                                      n_draws // len(batch_user), self._verify_tries)
+            for k, v in enumerate((n_draws, replaced, unresolved)):
+                counts[k] += v
+            return torch.from_numpy(np.ascontiguousarray(picked.reshape(-1))).to(device)
 
         for epoch_num in range(self._n_iter):
             arrays = shuffle(*((user_ids, item_ids) + ((weights,) if weights is not None else ())), random_state=self._random_state)
@@ -596,6 +672,8 @@ class ImplicitFactorizationModel(object):
                 n_mb += 1
             epoch_loss /= n_mb
             _epochs.end_epoch(epoch_num, epoch_loss, verbose)
+        if seen is not None:
+            self._store_verification(*counts)
 
     def predict(self, user_ids, item_ids=None):
         """Scores for one user against all/some items, or for explicit (user, item) pairs;

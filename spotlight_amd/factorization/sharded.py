@@ -335,7 +335,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
     All four losses (adaptive hinge: a score phase and a selection over the whole minibatch in front of the user pass,
     ShardedBilinearTrainer.run_chunk); loss='warp' is not built here and raises NotImplementedError at construction, before
     anything is drawn.  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
-    sharded yet: use_weights=True raises ValueError at construction.
+    sharded yet: use_weights=True raises ValueError at construction.  Verified negatives are not built here either:
+    verify_negatives=True raises NotImplementedError at construction, before anything is drawn.
 
     Evaluation runs shard by shard as well: evaluation.mrr_score (_fused_ranks), precision_recall_score (_batch_scores) and
     predict(user) sweep every rank's own item rows and combine the ranks' target scores (MAX), integer counts (SUM) or score
@@ -347,6 +348,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         # (before the base constructor: it draws the model's seed from random_state)
         if kwargs.get('loss', args[0] if args else 'pointwise') == 'warp':
             raise NotImplementedError("loss='warp': warp is not built on the row-sharded path")
+        if kwargs.get('verify_negatives', args[15] if len(args) > 15 else False):
+            raise NotImplementedError('verify_negatives=True: verified negatives are not built on the row-sharded path')
         super(ShardedImplicitFactorizationModel, self).__init__(*args, **kwargs)
         if self._use_weights:
             raise ValueError('use_weights=True is not supported by the row-sharded path: interaction weights are not sharded yet')

@@ -7,6 +7,9 @@ happens on the GPU (csrc/slk_rng.hip) from the very same MT19937 stream, bit-exa
 Uniform negatives are `RandomState.randint`; with item weights (`p`, an `ItemDistribution`) a draw is
 `RandomState.choice(num_items, size=shape, p=p)` -- on the device too (slk_sample_items_weighted), bit for bit and with
 the RandomState left where numpy leaves it.
+
+Verified negatives (`SeenItems`, `verify_negatives`): of several candidates drawn up front per negative slot, the first one the
+user has not interacted with -- slk_verify_negatives on the device, restated here in numpy for one minibatch.
 """
 import numpy as np
 
@@ -79,6 +82,131 @@ class ItemDistribution(object):
             raise RuntimeError('ItemDistribution.bind() has not been called')
         engine.sample_items_weighted(self.d_cdf.data_ptr(), self.d_guide.data_ptr(), self.guide_bits, self.num_items, count, d_out,
                                      stream)
+
+
+VERIFY_TRIES_MAX = 16  # include/spotlight_hip.h: slk_verify_negatives
+
+
+def check_verify_tries(verify_tries):
+    """The constructor-time check of a model's `verify_tries` argument: an int in [1, VERIFY_TRIES_MAX]."""
+    if (isinstance(verify_tries, bool) or not isinstance(verify_tries, (int, np.integer))
+            or not 1 <= verify_tries <= VERIFY_TRIES_MAX):
+        raise ValueError('verify_tries must be an int in [1, {}], got {!r}'.format(VERIFY_TRIES_MAX, verify_tries))
+    return int(verify_tries)
+
+
+class SeenItems(object):
+    """The users' histories that verified negatives are checked against (`verify_negatives=True`): the (user, item) pairs of
+    the fit() call in progress as a CSR over users -- int64 offsets [num_users + 1], int64 items ascending inside a user's
+    segment, duplicates kept (include/spotlight_hip.h: slk_verify_negatives).
+
+    `from_interactions` validates; `bind` builds the CSR on the device, once per fit(); `csr()` is the same CSR on the host,
+    built on first use (the numpy restatement `verify_negatives` reads it).  The device tensors are not pickled: the next
+    bind rebuilds them."""
+
+    def __init__(self, user_ids, item_ids, num_users, num_items):
+        self.user_ids, self.item_ids = user_ids, item_ids
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.d_off = self.d_items = None
+        self._csr = self._keys = None
+
+    @classmethod
+    def from_interactions(cls, user_ids, item_ids, num_users, num_items):
+        """ValueError unless the two id arrays are one-dimensional integer arrays of one length with every id in range."""
+        user_ids, item_ids = np.asarray(user_ids), np.asarray(item_ids)
+        if user_ids.ndim != 1 or item_ids.ndim != 1 or len(user_ids) != len(item_ids):
+            raise ValueError('verify_negatives: one user id and one item id per interaction are needed')
+        for name, ids, bound in (('user', user_ids, num_users), ('item', item_ids, num_items)):
+            if ids.dtype.kind not in 'iu':
+                raise ValueError('verify_negatives: {} ids must be integers'.format(name))
+            if ids.size and (ids.min() < 0 or ids.max() >= int(bound)):
+                raise ValueError('verify_negatives: {} ids must be in [0, {})'.format(name, int(bound)))
+        return cls(user_ids, item_ids, num_users, num_items)
+
+    def __len__(self):
+        return len(self.user_ids)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['d_off'] = state['d_items'] = None  # device tensors: rebuilt by the next bind()
+        state['_csr'] = state['_keys'] = None  # (and the host forms by their next use)
+        return state
+
+    def csr(self):
+        """(offsets int64 [num_users + 1], items int64) on the host."""
+        if self._csr is None:
+            users = np.asarray(self.user_ids, dtype=np.int64)
+            items = np.asarray(self.item_ids, dtype=np.int64)
+            order = np.lexsort((items, users))
+            off = np.zeros(self.num_users + 1, dtype=np.int64)
+            np.cumsum(np.bincount(users, minlength=self.num_users), out=off[1:])
+            self._csr = (off, np.ascontiguousarray(items[order]))
+        return self._csr
+
+    def packed_keys(self):
+        """The pairs as ascending int64 keys user * num_items + item (host; what `verify_negatives` searches)."""
+        if self._keys is None:
+            self._keys = _packed_keys(*self.csr(), self.num_items)
+        return self._keys
+
+    def bind(self, engine, device, stream=0, ids=None):
+        """The CSR on `device` (idempotent per device); returns self.  `ids`: the (users, items) int64 tensors if they are on
+        the device already.  Set-up, not the epoch path: one sort of the packed key user * num_items + item (two stable sorts
+        where the key does not fit 63 bits), stock tensor ops on the device."""
+        import torch
+        device = torch.device(device)
+        if self.d_off is not None and self.d_off.device == device:
+            return self
+        if ids is None:
+            ids = [torch.from_numpy(np.ascontiguousarray(a).astype(np.int64, copy=False)).to(device)
+                   for a in (self.user_ids, self.item_ids)]
+        users, items = ids
+        if self.num_users * self.num_items < 1 << 63:
+            key = torch.sort(users * self.num_items + items).values
+            d_items = key % self.num_items
+            bounds = torch.arange(self.num_users + 1, dtype=torch.int64, device=device) * self.num_items
+            d_off = torch.searchsorted(key, bounds)
+        else:
+            by_item = torch.sort(items, stable=True)
+            by_user = torch.sort(users[by_item.indices], stable=True)
+            d_items = by_item.values[by_user.indices]
+            d_off = torch.searchsorted(by_user.values, torch.arange(self.num_users + 1, dtype=torch.int64, device=device))
+        if device.type == 'cuda':
+            torch.cuda.synchronize(device)  # once per fit(): the kernel may run on another stream (the prep lane)
+        self.d_off, self.d_items = d_off.contiguous(), d_items.contiguous()
+        return self
+
+
+def _packed_keys(off, items, span):
+    """The (user, item) pairs of a CSR as ascending packed keys user * span + item."""
+    rows = np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+    return rows * span + items[:len(rows)]
+
+
+def verify_negatives(candidates, users, seen, n_neg, tries):
+    """The rule of slk_verify_negatives (include/spotlight_hip.h) for ONE minibatch, in numpy: `candidates` are the
+    tries * n_neg * bm ids of one draw for the bm `users` (viewed [tries][n_neg][bm]), `seen` a SeenItems or an
+    (offsets, items) CSR.  Returns (negatives int64 [n_neg, bm], replaced, unresolved): per slot the first attempt's candidate
+    that is not in the user's history -- attempt 0's, counted as unresolved, if every attempt is."""
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    bm = users.shape[0]
+    cand = np.asarray(candidates, dtype=np.int64).reshape(int(tries), int(n_neg), bm)
+    if isinstance(seen, SeenItems):
+        span, keys = seen.num_items, seen.packed_keys()
+    else:
+        off, items = np.asarray(seen[0], dtype=np.int64), np.asarray(seen[1], dtype=np.int64)
+        span = int(max(items.max() if items.size else 0, cand.max() if cand.size else 0)) + 1
+        keys = _packed_keys(off, items, span)
+    query = users[None, None, :] * span + cand
+    if len(keys):
+        at = np.minimum(np.searchsorted(keys, query), len(keys) - 1)
+        unseen = keys[at] != query
+    else:
+        unseen = np.ones(cand.shape, dtype=bool)
+    resolved = unseen.any(axis=0)
+    first = np.where(resolved, unseen.argmax(axis=0), 0)  # the smallest attempt with an unseen candidate
+    out = np.take_along_axis(cand, first[None], axis=0)[0]
+    return out, int((first > 0).sum()), int((~resolved).sum())
 
 
 def check_negative_sampling(negative_sampling):
