@@ -226,6 +226,10 @@ const char *slk_last_error(const slk_ctx *ctx); /* ctx may be NULL: last create 
  *                         256-thread workgroup per user), shorter ones the wave route (one wavefront per user); 0, the default:
  *                         the measured crossover.  A test and measurement switch, and like "adaptive_late_min_batch" NOT
  *                         bit-neutral: the two routes add a user's gradient terms in different (each fixed) orders
+ *   "als_wg_min_len"      slk_als_solve: histories of at least this many entries take the workgroup route (one 256-thread
+ *                         workgroup per row), shorter ones the light route (one wavefront per row); 0, the default: 32,
+ *                         the best of the values measured (8 .. 4096 and never: scripts/bench_als.py).  A test and measurement switch: both routes run the same chain of operations
+ *                         for every element, a row's bits are the same under every value
  *   "weighted_max_values" slk_sample_items_weighted: values one internal draw produces (default 2^27: 1 GiB of generated words;
  *                         at most 312 * (2^31 - 2), the generator's block limit); a larger count is a run of consecutive
  *                         draws.  A test and measurement switch: ids and final state are the same under every value */
@@ -825,6 +829,41 @@ int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_row
 int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_off, const int64_t *d_items,
                         int64_t n_new_users, int64_t n, int32_t loss, int32_t n_neg, int64_t n_steps, const int64_t *d_neg,
                         float *d_loss /* NULL or [n_steps][n_new_users] */, void *stream);
+
+/* Alternating least squares for implicit feedback (added to ABI 14: three new entries, nothing existing changes,
+ * SLK_ABI_VERSION stays).  The reference has no such trainer; the objective is Hu, Koren and Volinsky's confidence-weighted
+ * one, with p_ui = 1 for observed pairs and c_ui = 1 + w_ui:
+ *     L = sum over ALL (u, i) of c_ui (p_ui - x_u . y_i)^2 + lambda (sum_u |x_u|^2 + sum_i |y_i|^2).
+ * A half-step fixes one table Y [n][dim] (dense fp32, row-major) and sets every row u of the other side to the exact minimiser
+ *     x_u = (G + lambda I + sum_{i in N(u)} w_ui y_i y_i^T)^-1 sum_{i in N(u)} (w_ui + 1) y_i,       G = Y^T Y,
+ * N(u) and w_ui given as a CSR: d_off[rows + 1] (int64), d_cols (int64 row ids of Y) and d_vals (fp32 w = c - 1), duplicates
+ * already merged by the caller.  Ids are NOT range-checked (spotlight_amd builds the CSR from checked ids).
+ *
+ * slk_als_gram: d_gram[dim][dim] = Y^T Y over d_table[n_rows][dim].  Formed on the vector unit: per-workgroup partial tiles
+ *   over fixed sets of rows (a function of n_rows alone), added in workgroup order -- no float atomics; two calls give the same
+ *   bits and the result is symmetric bit for bit.  n_rows == 0 gives zeros.  Scratch: the partial tiles, in the ctx.
+ * slk_als_solve: the half-step for n_rows units.  Unit r solves row u = d_rows[r] (d_rows == NULL: u = r): it reads the CSR
+ *   segment of u and writes d_out[u][0 .. dim); the ids in d_rows must be distinct.  One unit owns one row from start to
+ *   finish: the system is built in LDS, factored by Cholesky (fp32, explicit fused multiply-adds), substituted twice, and dim
+ *   floats are written.  No scratch, no atomics except the failure counter, no host wait.  Histories of at least
+ *   "als_wg_min_len" entries take a 256-thread workgroup, shorter ones one wavefront; the order of every sum is fixed by the
+ *   position of an entry in the row's own segment, so a row's bits depend on its segment, d_fixed, d_gram and lambda and on
+ *   nothing else in the call -- not on the route, the grid, d_rows or the other rows.  An empty history gives the zero row.
+ *   A pivot that is not positive or not finite leaves that row of d_out untouched and adds 1 to *d_failed (a device int32
+ *   the caller has zeroed; the other rows are solved).  d_fixed and d_gram are read-only.
+ * slk_als_loss: d_out[u] (float64) = x_u^T G x_u + sum_{i in N(u)} [c_ui (1 - s_ui)^2 - s_ui^2] + lambda |x_u|^2 with
+ *   s_ui = x_u . y_i and x_u = d_rows_table[u], for u = 0 .. n_rows - 1, accumulated in float64.  Summed over u, plus
+ *   lambda sum_i |y_i|^2, this is L: the unobserved pairs cost s^2 each, x^T G x in all, at the price of the observed ones.
+ * dim: every dim <= 128 with a row layout (dim % 4 == 0, or dim <= 64).  Refused with SLK_EINVAL: another dim, a NULL
+ * pointer (d_rows excepted), a negative count, n_rows >= 2^31 (solve, loss), a lambda that is negative or not finite, and a
+ * table that is the user table of an open ping-pong scope (the array holds only some of the current rows).  Nothing is
+ * retained.  Profiled: slk_als_gram and slk_als_loss under SLK_K_SCORE, slk_als_solve under SLK_K_USER_PASS. */
+int slk_als_gram(slk_ctx *ctx, const float *d_table, int64_t n_rows, int64_t dim, float *d_gram, void *stream);
+int slk_als_solve(slk_ctx *ctx, const float *d_fixed, const float *d_gram, int64_t dim, float lambda, const int64_t *d_off,
+                  const int64_t *d_cols, const float *d_vals, const int64_t *d_rows /* NULL: rows 0 .. n_rows - 1 */,
+                  int64_t n_rows, float *d_out, int32_t *d_failed, void *stream);
+int slk_als_loss(slk_ctx *ctx, const float *d_rows_table, const float *d_fixed, const float *d_gram, int64_t dim, float lambda,
+                 const int64_t *d_off, const int64_t *d_cols, const float *d_vals, int64_t n_rows, double *d_out, void *stream);
 
 /* Measurement support (the reference has none; examples/bloom_embeddings/performance.py
  * times fit() with time.time()): when enabled, every launch of the engine's kernels is

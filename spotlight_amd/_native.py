@@ -85,6 +85,11 @@ _PROTOTYPES = {
                                        C.c_int32, C.c_int32, C.c_void_p]),
     'slk_bilinear_foldin': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_als_gram': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'slk_als_solve': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'slk_als_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'slk_bilinear_predict': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'slk_poolnet_train': (C.c_int, [C.c_void_p, C.POINTER(SlkTables), C.POINTER(SlkOptim), C.c_int64, C.c_void_p,
@@ -432,6 +437,23 @@ class Engine(object):
         self._check(self._lib.slk_bilinear_foldin(
             self._ctx, C.byref(tables), C.byref(optim), d_off, d_items, int(n_new_users), int(n),
             LOSS_KINDS[loss] if isinstance(loss, str) else int(loss), int(n_neg), int(n_steps), d_neg, d_loss, stream))
+
+    # -- alternating least squares (include/spotlight_hip.h: slk_als_gram / _solve / _loss) --------
+    def als_gram(self, d_table, n_rows, dim, d_gram, stream=0):
+        """d_gram[dim][dim] = Y^T Y over the dense fp32 table d_table[n_rows][dim]; deterministic, symmetric bit for bit."""
+        self._check(self._lib.slk_als_gram(self._ctx, d_table, int(n_rows), int(dim), d_gram, stream))
+
+    def als_solve(self, d_fixed, d_gram, dim, regularization, d_off, d_cols, d_vals, d_rows, n_rows, d_out, d_failed, stream=0):
+        """One ALS half-step: row u = d_rows[r] (None: u = r) of d_out becomes the exact minimiser of its system, built from the CSR
+        segment of u (d_off / d_cols / d_vals = c - 1) against the fixed table and its Gram matrix; *d_failed (a zeroed device
+        int32) counts the rows whose system was not positive definite in fp32, which are left untouched."""
+        self._check(self._lib.slk_als_solve(self._ctx, d_fixed, d_gram, int(dim), float(regularization), d_off, d_cols, d_vals, d_rows,
+                                            int(n_rows), d_out, d_failed, stream))
+
+    def als_loss(self, d_rows_table, d_fixed, d_gram, dim, regularization, d_off, d_cols, d_vals, n_rows, d_out, stream=0):
+        """d_out[u] (float64) = the objective's terms of row u over ALL columns plus lambda |x_u|^2."""
+        self._check(self._lib.slk_als_loss(self._ctx, d_rows_table, d_fixed, d_gram, int(dim), float(regularization), d_off, d_cols,
+                                           d_vals, int(n_rows), d_out, stream))
 
     def bilinear_predict(self, tables, d_users, n_users, d_items, n, d_out, stream=0):
         self._check(self._lib.slk_bilinear_predict(self._ctx, C.byref(tables), d_users, int(n_users),

@@ -261,6 +261,10 @@ const slk_opt_desc slk_eval_options[] = {
     // the default, all-workgroup and all-wave
     {"foldin_wg_min_len", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_foldin_wg_min_len; },
      [](slk_ctx *c, int64_t v) { c->opt_foldin_wg_min_len = v; }},
+    // slk_als_solve's route choice.  Both routes run the same chains of operations per element, so the value IS bit-neutral;
+    // tests/als_checks.py solves every system under the default, all-workgroup and all-light
+    {"als_wg_min_len", 0, (int64_t)1 << 40, [](const slk_ctx *c) -> int64_t { return c->opt_als_wg_min_len; },
+     [](slk_ctx *c, int64_t v) { c->opt_als_wg_min_len = v; }},
     // slk_sample_items_weighted: values per internal draw (the split of a large count); tests/weighted_sampler_checks.py
     // draws the same ids and ends in the same state under a limit of 100
     {"weighted_max_values", 1, (int64_t)0x7ffffffe * 312, [](const slk_ctx *c) -> int64_t { return c->opt_weighted_max_values; },

@@ -130,6 +130,8 @@ enum slk_extra_slot {
     EV_REP = 24, EV_RBIAS, EV_ST = 37, EV_CNT = 39, EV_TOPK = 50, EV_TOPK_FLAG,
     // slk_bilinear.hip, a weighted training call: the float64 weight sums of a chunk's minibatches and their per-segment partials
     BL_WSUM = 52, BL_WPART,
+    // slk_als.hip: the partial tiles of slk_als_gram (nothing survives the call)
+    AL_GPART = 54,
     SLK_EXTRA_END  // (the slots above are the highest in use)
 };
 static_assert(SLK_EXTRA_END <= SLK_EXTRA_BUFS, "slk_ctx::extra holds every slot of slk_extra_slot");
@@ -250,6 +252,9 @@ struct slk_ctx {
                                       // the same kind of switch
     int64_t opt_foldin_wg_min_len = 0;  // slk_bilinear_foldin: histories of at least this many interactions take the workgroup route (0: the
                                       // measured default, SLK_FOLDIN_WG_MIN_LEN in slk_foldin.hip); a test / measurement switch
+    int64_t opt_als_wg_min_len = 0;   // slk_als_solve: histories of at least this many entries take the workgroup route (0: the best of
+                                      // the values measured, SLK_ALS_WG_MIN_LEN in slk_als.hip); a test / measurement switch, the result does not
+                                      // depend on it
     int64_t opt_weighted_max_values = (int64_t)1 << 27;  // slk_sample_items_weighted: values per internal draw (2^27: 1 GiB of generated
                                       // words); a larger count is a run of consecutive draws.  A test / measurement switch, the result
                                       // does not depend on it
