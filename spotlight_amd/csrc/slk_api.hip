@@ -54,6 +54,23 @@ int slk_ensure_lflags_host(slk_ctx *ctx, slk_prep_bufs &pb, size_t n) {
     return SLK_OK;
 }
 
+int slk_lflags_readback(slk_ctx *ctx, slk_prep_bufs &pb, size_t n, hipStream_t s) {
+    int rc;
+    if ((rc = slk_ensure_lflags_host(ctx, pb, n))) return rc;
+    SLK_HIP(ctx, hipMemcpyAsync(pb.h_lflags, pb.lflags.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
+    SLK_HIP(ctx, hipEventRecord(pb.ev_lflags, s));
+    return SLK_OK;
+}
+
+int slk_lflags_reserve(slk_ctx *ctx, slk_prep_bufs &pb, size_t n) {
+    int rc;
+    if ((rc = slk_ensure_lflags_host(ctx, pb, n))) return rc;
+    pb.h_lflags_n = 0;
+    if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
+    return SLK_OK;
+}
+
 void slk_prof_begin(slk_ctx *ctx, int cls, hipStream_t s) {
     if (!ctx->prof_on) return;
     slk_prof_span sp;
@@ -181,7 +198,7 @@ SLK_EXPORT void slk_ctx_destroy(slk_ctx *ctx) {
     for (slk_prep_bufs &pb : ctx->pb) {
         slk_buf *pbs[] = {&pb.neg32, &pb.ukey[0], &pb.ukey[1], &pb.uval[0], &pb.uval[1], &pb.uit, &pb.ikey[0],
                           &pb.ikey[1], &pb.ipay[0], &pb.ipay[1], &pb.bik[0], &pb.bik[1], &pb.bip[0], &pb.bip[1],
-                          &pb.buk[0], &pb.buk[1], &pb.bup[0], &pb.bup[1], &pb.lflags, &pb.mflag, &pb.msorted};
+                          &pb.buk[0], &pb.buk[1], &pb.bup[0], &pb.bup[1], &pb.lflags, &pb.mflag, &pb.msorted, &pb.mcount};
         for (slk_buf *b : pbs)
             if (b->p) (void)hipFree(b->p);
         if (pb.ev_lflags) (void)hipEventDestroy(pb.ev_lflags);

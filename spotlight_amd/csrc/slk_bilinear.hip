@@ -1056,6 +1056,23 @@ int slk_launch_i64_to_u32(slk_ctx *ctx, const int64_t *in, uint32_t *out, size_t
     return SLK_OK;
 }
 
+int slk_prep_given_negatives(slk_ctx *ctx, const int64_t *neg_in, int64_t *neg_out, size_t n, slk_prep_bufs &pb, hipStream_t s) {
+    int rc;
+    slk_prof_begin(ctx, SLK_K_SAMPLE, s);
+    if ((rc = slk_launch_i64_to_u32(ctx, neg_in, (uint32_t *)pb.neg32.p, n, s))) return rc;
+    if (neg_out) SLK_HIP(ctx, hipMemcpyAsync(neg_out, neg_in, n * 8, hipMemcpyDeviceToDevice, s));
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+void slk_fill_table_args(slk_pass_args &a, const slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, bool dense) {
+    for (int t = 0; t < 4; ++t) {
+        a.P[t] = tables->d_param[t];
+        a.S1[t] = dense ? (float *)ctx->dgrad[t].p : optim->d_state1[t];
+        a.S2[t] = optim->d_state2[t];
+    }
+}
+
 SLK_EXPORT int slk_bilinear_predict(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_users,
                                     int64_t n_users, const int64_t *d_items, int64_t n, float *d_out,
                                     void *stream) {
@@ -1483,12 +1500,8 @@ static int reserve_extras(slk_ctx *ctx, const train_plan &p, const train_call &c
     if (p.side && (rc = slk_prep_stream_init(ctx))) return rc;
     // the pinned read-back buffers and events of the long-run flags, per buffer set: hipHostMalloc inside a training call
     // costs a device synchronisation (measured: the first overlapped call of a process 0.85 instead of 0.745 ms per step)
-    for (int st = 0; st < p.nsets; ++st) {
-        slk_prep_bufs &pb = ctx->pb[st];
-        if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)p.mb_per_chunk))) return rc;
-        pb.h_lflags_n = 0;
-        if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
-    }
+    for (int st = 0; st < p.nsets; ++st)
+        if ((rc = slk_lflags_reserve(ctx, ctx->pb[st], 2 * (size_t)p.mb_per_chunk))) return rc;
     if (p.side && !ctx->prep_warmed && p.nn > 0 && p.nc_max >= 4096 && (rc = warm_prep_stream(ctx, p, c))) return rc;
     const uint32_t n_mb = (uint32_t)((p.nc_max + p.bsz - 1) / p.bsz);
     if (p.epoch_route && (rc = slk_epoch_reserve(ctx, c.tables, c.optim, n_mb, p.bsz, (int)c.loss, p.NP))) return rc;
@@ -1556,15 +1569,7 @@ static int prep_sample(slk_ctx *ctx, const train_plan &p, const train_call &c, c
 
     // ---- negatives (sampling.py:34, one randint per minibatch == one contiguous draw)
     if (p.nn == 0) return SLK_OK;  // explicit feedback draws none
-    if (c.neg_in) {
-        slk_prof_begin(ctx, SLK_K_SAMPLE, s);
-        hipLaunchKernelGGL(k_i64_to_u32, dim3(slk_grid_for(ctx, nneg, 256)), dim3(256), 0, s, c.neg_in + c0 * p.nn, u32p(pb.neg32), nneg);
-        SLK_LAUNCH_CHECK(ctx, "k_i64_to_u32");
-        if (c.neg_out)
-            SLK_HIP(ctx, hipMemcpyAsync(c.neg_out + c0 * p.nn, c.neg_in + c0 * p.nn, nneg * 8, hipMemcpyDeviceToDevice, s));
-        slk_prof_end(ctx, s);
-        return SLK_OK;
-    }
+    if (c.neg_in) return slk_prep_given_negatives(ctx, c.neg_in + c0 * p.nn, c.neg_out ? c.neg_out + c0 * p.nn : nullptr, nneg, pb, s);
     return slk_sample_u32(ctx, c.tables->num_items, (int64_t)nneg, u32p(pb.neg32), c.neg_out ? c.neg_out + c0 * p.nn : nullptr, s);
 }
 
@@ -1637,10 +1642,7 @@ static int prep_sort(slk_ctx *ctx, const train_plan &p, const train_call &c, con
                                (const uint32_t *)ukey, nc, bsz, (int *)pb.lflags.p + n_mb_c);
             SLK_LAUNCH_CHECK(ctx, "k_user_long_flags");
         }
-        if ((rc = slk_ensure_lflags_host(ctx, pb, 2 * (size_t)n_mb_c))) return rc;
-        SLK_HIP(ctx, hipMemcpyAsync(pb.h_lflags, pb.lflags.p, 2 * (size_t)n_mb_c * 4, hipMemcpyDeviceToHost, s));
-        if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
-        SLK_HIP(ctx, hipEventRecord(pb.ev_lflags, s));
+        if ((rc = slk_lflags_readback(ctx, pb, 2 * (size_t)n_mb_c, s))) return rc;
     } else {
         pb.h_lflags_n = 0;  // no flags for this chunk: every pass of a fall-back takes the partial-writing form
     }
@@ -1681,11 +1683,7 @@ static void chunk_pass_args(slk_ctx *ctx, const train_plan &p, const train_call 
     const slk_tables *tables = c.tables;
     const slk_optim *optim = c.optim;
     memset(&a, 0, sizeof(a));
-    for (int t = 0; t < 4; ++t) {
-        a.P[t] = tables->d_param[t];
-        a.S1[t] = p.dense ? f32p(ctx->dgrad[t]) : optim->d_state1[t];
-        a.S2[t] = optim->d_state2[t];
-    }
+    slk_fill_table_args(a, ctx, tables, optim, p.dense);
     if (p.shadowed) {
         a.P[3] = f32p(ctx->bias_shadow);
         a.S1[3] = f32p(ctx->bias_shadow) + 1;

@@ -112,11 +112,10 @@ enum slk_extra_slot {
     TS_T0 = 26, TS_T1, TS_T2, TS_T3, TS_T4, TS_SMALL, TS_SORT, TS_USERS, TS_ITEMS, TS_HEADS, TS_ROWOFF,
     // slk_shuffle.hip, one slk_shuffle_perm call
     FY_B0 = TS_T0, FY_B1, FY_B2, FY_B3, FY_B4, FY_SMALL, FY_SORT,  // safe: temporaries of one call on either side
-    // slk_seq.hip, the training call and slk_poolnet_predict (nothing survives either)
-    SQ_MCOUNT = 12, SQ_REP, SQ_BIK0, SQ_BIK1,
-    SQ_BIP0 = BL_UREC, SQ_BIP1,  // safe: no code names SQ_BIK0..SQ_BIP1 (the bloom occurrence lists moved into slk_prep_bufs)
+    // slk_seq.hip: SQ_REP slk_poolnet_predict's representation, SQ_GSN the training call's dL/dscore (nothing survives either;
+    // what the call's prep fills per buffer set -- mask counts, occurrence lists -- lives in slk_prep_bufs)
+    SQ_REP = 13,
     SQ_GSN = BL_UPART,           // safe: either side fills and reads it inside one training call
-    SQ_MCOUNT_B = TS_T4,         // safe: the second prep set's mask counts, written and read inside one training call
     // slk_embed.hip: EM_KEY0..EM_HEADS hold the plan from slk_embedding_backward_plan until slk_embedding_backward_fill
     EM_SORT = TS_SORT,  // safe: the radix sort's scratch, dead when the sort returns
     EM_KEY0 = 40, EM_KEY1, EM_PAY0, EM_PAY1, EM_HEADS, EM_PART0, EM_PART1,
@@ -136,10 +135,11 @@ enum slk_extra_slot {
 };
 static_assert(SLK_EXTRA_END <= SLK_EXTRA_BUFS, "slk_ctx::extra holds every slot of slk_extra_slot");
 
-// buffers filled by the value-independent prep of one chunk of minibatches (slk_bilinear.hip)
+// buffers filled by the value-independent prep of one chunk of minibatches (slk_bilinear.hip, slk_seq.hip)
 struct slk_prep_bufs {
     slk_buf neg32, ukey[2], uval[2], uit, ikey[2], ipay[2];
     slk_buf bik[2], bip[2], buk[2], bup[2];  // BloomEmbedding hashed-row occurrence lists
+    slk_buf mcount;                 // slk_seq.hip: mask.sum() per minibatch of the chunk (k_seq_count)
     slk_buf mflag, msorted;         // single-occurrence fast path: "the item occurs more than once in its minibatch" per occurrence
     slk_buf lflags;                 // per minibatch of the chunk: does a run of the item-sorted list wholly cover a tile?
     int *h_lflags = nullptr;        //   (k_item_long_flags; read back once per chunk into PINNED host memory -- a pageable
@@ -328,6 +328,11 @@ struct slk_ctx {
 int slk_fail(slk_ctx *ctx, int code, const char *fmt, ...);
 int slk_ensure(slk_ctx *ctx, slk_buf &b, size_t bytes);
 int slk_ensure_lflags_host(slk_ctx *ctx, slk_prep_bufs &pb, size_t n);  // pinned int[n], every entry 1 (= may hold a long run)
+// the long-run flags of a chunk's prep, for both training drivers: behind the flag kernels on `s`, pb.lflags[0, n) is read back
+// into the pinned array and pb.ev_lflags recorded behind the copy (the passes' host wait); _reserve: what that would
+// otherwise allocate inside a training call (hipHostMalloc there costs a device synchronisation), no flags noted
+int slk_lflags_readback(slk_ctx *ctx, slk_prep_bufs &pb, size_t n, hipStream_t s);
+int slk_lflags_reserve(slk_ctx *ctx, slk_prep_bufs &pb, size_t n);
 void slk_prof_begin(slk_ctx *ctx, int cls, hipStream_t s);
 void slk_prof_end(slk_ctx *ctx, hipStream_t s);
 int slk_prof_drain(slk_ctx *ctx);
@@ -428,6 +433,12 @@ int slk_eval_user_rep(slk_ctx *ctx, const slk_tables *tables, int vec, int g, co
 int slk_check_tables(slk_ctx *ctx, const slk_tables *t, unsigned table_mask, int *vec, int *g, bool shadow_ok = false,
                      bool pingpong_ok = false);
 int slk_launch_i64_to_u32(slk_ctx *ctx, const int64_t *in, uint32_t *out, size_t n, hipStream_t s);
+// the negatives a training call was handed, for one chunk (`n` of them from neg_in): as uint32 into pb.neg32, echoed to
+// neg_out unless that is NULL; one SLK_K_SAMPLE span
+int slk_prep_given_negatives(slk_ctx *ctx, const int64_t *neg_in, int64_t *neg_out, size_t n, slk_prep_bufs &pb, hipStream_t s);
+// P / S1 / S2 of a pass: the tables, and the optimizer's state -- S1 of a *_DENSE optimizer is the ctx's gradient buffer
+struct slk_pass_args;
+void slk_fill_table_args(slk_pass_args &a, const slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, bool dense);
 
 int slk_sort_reserve(slk_ctx *ctx, size_t n);
 int64_t slk_sort_finish_cap(void);  // pairs a bucket of the top-digit route may hold (slk_ctx_get_stat "sort_finish_cap")

@@ -581,348 +581,437 @@ __global__ __launch_bounds__(256) void k_seq_predict(const float *rep, const flo
 
 typedef void (*seq_pass_fn)(slk_seq_args);
 
-static int poolnet_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, int64_t padding_idx,
-                              const int64_t *d_sequences, int64_t n_seq, int64_t seq_len, int64_t batch_size,
-                              int32_t loss, int32_t n_neg, const int64_t *d_neg_in, int64_t *d_neg_out,
-                              float *d_mb_loss, void *stream, bool reserve_only);
+// ---------------------------------------------------------------------------------------------------------------------------
+// The sequence training driver, laid out as the bilinear one (slk_bilinear.hip, above train_call).  A call is (1) taken down
+// as given (seq_call), (2) planned: every derived value and every refusal, before any GPU work (plan_seq_training), (3) given
+// its scratch (ensure_seq_scratch) and (4) its kernels (pick_seq_kernels; slk_poolnet_reserve stops behind them, in
+// reserve_seq_extras), and (5) scheduled: chunk by chunk, the value-independent prep of a chunk (seq_prep_sample,
+// seq_prep_sort) and its minibatches (run_seq_passes: sequence pass, item_stage, dense sweeps) in line (run_seq_inline) or
+// one chunk ahead on the ctx's prep stream (run_seq_pipelined; option "overlap_prep", timesteps per minibatch >=
+// "overlap_min_batch").  The buffer sets (ctx->pb[0|1]), the prep stream and its events are the bilinear driver's.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct seq_call {  // the arguments as given
+    enum { TRAIN, RESERVE } mode;
+    const slk_tables *tables;
+    slk_optim *optim;
+    int64_t padding_idx;
+    const int64_t *sequences;
+    int64_t n_seq, seq_len, batch_size;
+    int32_t loss, n_neg;
+    const int64_t *neg_in;
+    int64_t *neg_out;
+    float *mb_loss;
+    hipStream_t s;
+};
+
+struct seq_plan {  // everything derived from a call and the ctx's options before any GPU work
+    int vec, g, D;
+    int64_t L;
+    int NG, DL;        // row groups per workgroup, floats of a staged row
+    size_t lds_bytes;  // the LDS-staged sequence pass: L item rows + two rows per row group
+    bool adaptive;
+    int nn, NP;
+    unsigned ibits, icbits, kbits;
+    slk_bloom_dev ibd;  // item_embedding_layer = BloomEmbedding (sequence/representations.py:62-68): hashed-row owner pass
+    int Hi;
+    int64_t bsz, mb_per_chunk, chunk_seqs;
+    // chunk ck is sequences [ck * chunk_seqs, min(n_seq, (ck + 1) * chunk_seqs)): ns_max sequences (nts_max timesteps) in the
+    // largest (= the first); 0 chunks: an empty call
+    int64_t n_chunks;
+    int nsets;
+    size_t ns_max, nts_max;
+    int64_t occ_mult;
+    int RS;  // record = [representation | history gradient], 16-B granular halves
+    unsigned max_grid;
+    bool dense;
+    size_t dense_elems[4];  // the *_DENSE optimizers' gradient buffers
+    bool reg_pass;          // register-resident sequence pass: a group's chunk of timesteps fits 16 rows of VGPRs
+    unsigned gpb;
+};
+
+struct seq_kernels {
+    seq_pass_fn spass;
+    slk_item_fns ipass, ipass_rows, ipass_bias;
+};
+
+static const unsigned SEQ_TABLES = 10u;  // tables 1 (item_embeddings) and 3 (item_biases)
+
+static inline int64_t chunk_begin(const seq_plan &p, int64_t ck) { return ck * p.chunk_seqs; }
+static inline uint32_t chunk_len(const seq_plan &p, const seq_call &c, int64_t ck) {
+    const int64_t c1 = chunk_begin(p, ck + 1);
+    return (uint32_t)((c1 < c.n_seq ? c1 : c.n_seq) - chunk_begin(p, ck));
+}
+
+static int run_seq_training(slk_ctx *ctx, const seq_call &c);
 
 SLK_EXPORT int slk_poolnet_train(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, int64_t padding_idx,
                                  const int64_t *d_sequences, int64_t n_seq, int64_t seq_len, int64_t batch_size,
                                  int32_t loss, int32_t n_neg, const int64_t *d_neg_in, int64_t *d_neg_out,
                                  float *d_mb_loss, void *stream) {
-    return poolnet_train_impl(ctx, tables, optim, padding_idx, d_sequences, n_seq, seq_len, batch_size, loss, n_neg,
-                              d_neg_in, d_neg_out, d_mb_loss, stream, false);
+    return run_seq_training(ctx, {seq_call::TRAIN, tables, optim, padding_idx, d_sequences, n_seq, seq_len, batch_size, loss,
+                                  n_neg, d_neg_in, d_neg_out, d_mb_loss, (hipStream_t)stream});
 }
 
 SLK_EXPORT int slk_poolnet_reserve(slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, int64_t n_seq,
                                    int64_t seq_len, int64_t batch_size, int32_t loss, int32_t n_neg, void *stream) {
     if (!optim) return slk_fail(ctx, SLK_EINVAL, "optim is NULL");
     slk_optim o = *optim;
-    return poolnet_train_impl(ctx, tables, &o, 0, nullptr, n_seq, seq_len, batch_size, loss, n_neg, nullptr, nullptr,
-                              nullptr, stream, true);
+    return run_seq_training(ctx, {seq_call::RESERVE, tables, &o, 0, nullptr, n_seq, seq_len, batch_size, loss, n_neg, nullptr,
+                                  nullptr, nullptr, (hipStream_t)stream});
 }
 
-static int poolnet_train_impl(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, int64_t padding_idx,
-                              const int64_t *d_sequences, int64_t n_seq, int64_t seq_len, int64_t batch_size,
-                              int32_t loss, int32_t n_neg, const int64_t *d_neg_in, int64_t *d_neg_out,
-                              float *d_mb_loss, void *stream, bool reserve_only) {
-    if (!ctx) return SLK_EINVAL;
-    int vec, g, rc;
-    const unsigned TM = 10u;  // tables 1 (item_embeddings) and 3 (item_biases)
-    if ((rc = slk_check_tables(ctx, tables, TM, &vec, &g))) return rc;
-    if ((rc = slk_check_optim(ctx, optim, TM))) return rc;
-    if (n_seq < 0 || batch_size < 1 || seq_len < 1)
+// Every derived value of a call and every refusal, in the order the rules have always been checked in (where a call breaks
+// several, the first one answers).  Touches nothing on the GPU; of the ctx only the current device and the noted stream.
+static int plan_seq_training(slk_ctx *ctx, const seq_call &c, seq_plan *plan) {
+    seq_plan &p = *plan;
+    const slk_tables *tables = c.tables;
+    const int64_t n_seq = c.n_seq;
+    int rc;
+    p.n_chunks = 0;
+    if ((rc = slk_check_tables(ctx, tables, SEQ_TABLES, &p.vec, &p.g))) return rc;
+    if ((rc = slk_check_optim(ctx, c.optim, SEQ_TABLES))) return rc;
+    if (n_seq < 0 || c.batch_size < 1 || c.seq_len < 1)
         return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: n_seq %lld batch_size %lld seq_len %lld", (long long)n_seq,
-                        (long long)batch_size, (long long)seq_len);
-    if (loss == SLK_LOSS_WARP)
-        return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: warp (loss kind %d) is not built for the sequence model", loss);
-    if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_ADAPTIVE_HINGE)
-        return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", loss);
-    const bool adaptive = loss == SLK_LOSS_ADAPTIVE_HINGE;
-    const int nn = adaptive ? n_neg : 1;
-    if (nn < 1 || nn > 1024) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", nn);
-    const int NP = nn + 1;
-    if (padding_idx < -1 || padding_idx >= tables->num_items)
-        return slk_fail(ctx, SLK_EINVAL, "padding_idx %lld outside [-1, num_items)", (long long)padding_idx);
+                        (long long)c.batch_size, (long long)c.seq_len);
+    if (c.loss == SLK_LOSS_WARP)
+        return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: warp (loss kind %d) is not built for the sequence model", c.loss);
+    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_ADAPTIVE_HINGE)
+        return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", c.loss);
+    p.adaptive = c.loss == SLK_LOSS_ADAPTIVE_HINGE;
+    p.nn = p.adaptive ? c.n_neg : 1;
+    if (p.nn < 1 || p.nn > 1024) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", p.nn);
+    p.NP = p.nn + 1;
+    if (c.padding_idx < -1 || c.padding_idx >= tables->num_items)
+        return slk_fail(ctx, SLK_EINVAL, "padding_idx %lld outside [-1, num_items)", (long long)c.padding_idx);
     if (n_seq == 0) return SLK_OK;
-    if (!reserve_only && (!d_sequences || !d_mb_loss)) return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: NULL pointer");
-    const int D = tables->dim;
-    const int64_t L = seq_len;
-    const int NG = 256 / g, DL = g * vec;
-    const size_t lds_bytes = ((size_t)L * DL + 2 * (size_t)NG * DL) * 4;
-    if (lds_bytes > 160 * 1024 - 4096)
-        return slk_fail(ctx, SLK_EINVAL, "sequence length %lld x dim %d does not fit the 160 KB LDS of a CU",
-                        (long long)L, D);
-    const int64_t bsz = batch_size < n_seq ? batch_size : n_seq;
-    if (bsz * L * NP * (tables->item_bloom ? tables->item_bloom->n_hash : 1) >= ((int64_t)1 << 31))
+    if (c.mode != seq_call::RESERVE && (!c.sequences || !c.mb_loss))
+        return slk_fail(ctx, SLK_EINVAL, "slk_poolnet_train: NULL pointer");
+    p.D = tables->dim;
+    const int64_t L = p.L = c.seq_len;
+    p.NG = 256 / p.g;
+    p.DL = p.g * p.vec;
+    p.lds_bytes = ((size_t)L * p.DL + 2 * (size_t)p.NG * p.DL) * 4;
+    if (p.lds_bytes > 160 * 1024 - 4096)
+        return slk_fail(ctx, SLK_EINVAL, "sequence length %lld x dim %d does not fit the 160 KB LDS of a CU", (long long)L, p.D);
+    const int64_t bsz = p.bsz = c.batch_size < n_seq ? c.batch_size : n_seq;
+    if (bsz * L * p.NP * (tables->item_bloom ? tables->item_bloom->n_hash : 1) >= ((int64_t)1 << 31))
         return slk_fail(ctx, SLK_EINVAL, "batch_size * seq_len * lookups per timestep must be < 2^31");
     SLK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    ctx->last_stream = s;
+    ctx->last_stream = c.s;
 
-    const unsigned ibits = slk_bits_for((uint64_t)tables->num_items - 1);
-    // item_embedding_layer = BloomEmbedding (sequence/representations.py:62-68): hashed-row owner pass
-    slk_bloom_dev ibd;
-    slk_bloom_to_dev(tables->item_bloom, &ibd);
-    const int Hi = ibd.n_hash;
-    const unsigned icbits = Hi ? slk_bits_for((uint64_t)ibd.rows - 1) : 0;
-    const unsigned kbits = icbits > ibits ? icbits : ibits;
+    p.ibits = slk_bits_for((uint64_t)tables->num_items - 1);
+    slk_bloom_to_dev(tables->item_bloom, &p.ibd);
+    const int Hi = p.Hi = p.ibd.n_hash;
+    p.icbits = Hi ? slk_bits_for((uint64_t)p.ibd.rows - 1) : 0;
+    p.kbits = p.icbits > p.ibits ? p.icbits : p.ibits;
     // minibatches per chunk: keys fit 32 bits, occurrences < 2^31, ~8M timesteps of scratch
-    int64_t mb_per_chunk = (int64_t)1 << (32 - kbits);
+    int64_t mb_per_chunk = (int64_t)1 << (32 - p.kbits);
     const int64_t cap_ts = ctx->opt_chunk_interactions;  // timesteps of scratch per chunk (~8M)
     if (mb_per_chunk > 32768) mb_per_chunk = 32768;  // gridDim.y of the mask-count launch
     if (mb_per_chunk * bsz * L > cap_ts) mb_per_chunk = cap_ts / (bsz * L);
-    const int64_t occ_mult = (int64_t)NP * (Hi ? Hi : 1);
-    while (mb_per_chunk > 1 && mb_per_chunk * bsz * L * occ_mult >= ((int64_t)1 << 31)) mb_per_chunk >>= 1;
+    p.occ_mult = (int64_t)p.NP * (Hi ? Hi : 1);
+    while (mb_per_chunk > 1 && mb_per_chunk * bsz * L * p.occ_mult >= ((int64_t)1 << 31)) mb_per_chunk >>= 1;
     if (mb_per_chunk < 1) mb_per_chunk = 1;
-    const int64_t chunk_seqs = mb_per_chunk * bsz;
-    const size_t ns_max = (size_t)(chunk_seqs < n_seq ? chunk_seqs : n_seq);
-    const size_t nts_max = ns_max * L;
+    p.mb_per_chunk = mb_per_chunk;
+    p.chunk_seqs = mb_per_chunk * bsz;
+    p.ns_max = (size_t)(p.chunk_seqs < n_seq ? p.chunk_seqs : n_seq);
+    p.nts_max = p.ns_max * L;
+    p.n_chunks = (n_seq + p.chunk_seqs - 1) / p.chunk_seqs;
+    // two buffer sets: chunk c + 1 is prepared on the ctx's second stream while chunk c's passes run
+    p.nsets = (ctx->opt_overlap_prep && p.n_chunks > 1 && bsz * L >= ctx->opt_overlap_min_batch) ? 2 : 1;
+    p.RS = 2 * ((p.D + 3) / 4 * 4);
+    p.max_grid = (unsigned)ctx->num_cus * 8;
+    p.dense = slk_opt_is_dense(c.optim->kind);
+    p.dense_elems[0] = p.dense_elems[2] = 0;
+    p.dense_elems[1] = (size_t)(Hi ? p.ibd.rows : tables->num_items) * p.D;
+    p.dense_elems[3] = (size_t)tables->num_items;
+    p.reg_pass = L <= 256 && (L + p.NG - 1) / p.NG <= 16 && ctx->opt_seq_variant != 0;
+    p.gpb = 256u / (unsigned)p.g;
+    return SLK_OK;
+}
 
-    // The value-independent prep of a chunk (negatives, mask counts, the sort of the occurrences by item, the long-run flags)
-    // is prepared on the ctx's second stream while the previous chunk's passes run, as in slk_bilinear_train (option
-    // "overlap_prep"; timesteps per minibatch >= "overlap_min_batch"): its buffers exist per set (ctx->pb[0|1]).
-    const int64_t n_chunks = (n_seq + chunk_seqs - 1) / chunk_seqs;
-    const int nsets = (ctx->opt_overlap_prep && n_chunks > 1 && bsz * L >= ctx->opt_overlap_min_batch) ? 2 : 1;
-    for (int st = 0; st < nsets; ++st) {
+// scratch: the per-set buffers of the value-independent prep (ctx->pb[0|1], one set unless the prep is pipelined), then what
+// the passes of one minibatch share
+static int ensure_seq_scratch(slk_ctx *ctx, const seq_plan &p, hipStream_t s) {
+    const size_t nts_max = p.nts_max, NP = (size_t)p.NP, Hi = (size_t)p.Hi;
+    int rc;
+    for (int st = 0; st < p.nsets; ++st) {
         slk_prep_bufs &pb = ctx->pb[st];
-        if ((rc = slk_ensure(ctx, pb.neg32, nts_max * nn * 4))) return rc;
+        if ((rc = slk_ensure(ctx, pb.neg32, nts_max * p.nn * 4))) return rc;
         for (int b = 0; b < 2; ++b) {
             if ((rc = slk_ensure(ctx, pb.ikey[b], nts_max * NP * 4))) return rc;
             if ((rc = slk_ensure(ctx, pb.ipay[b], nts_max * NP * 4))) return rc;
             if (Hi && (rc = slk_ensure(ctx, pb.bik[b], nts_max * NP * Hi * 4))) return rc;
             if (Hi && (rc = slk_ensure(ctx, pb.bip[b], nts_max * NP * Hi * 4))) return rc;
         }
-        if ((rc = slk_ensure(ctx, pb.lflags, (size_t)mb_per_chunk * 4))) return rc;
-        if ((rc = slk_ensure(ctx, ctx->extra[SQ_MCOUNT + (st ? SQ_MCOUNT_B - SQ_MCOUNT : 0)], (size_t)mb_per_chunk * 4))) return rc;
+        if ((rc = slk_ensure(ctx, pb.lflags, (size_t)p.mb_per_chunk * 4))) return rc;
+        if ((rc = slk_ensure(ctx, pb.mcount, (size_t)p.mb_per_chunk * 4))) return rc;
     }
-    const int RS = 2 * ((D + 3) / 4 * 4);  // record = [representation | history gradient], 16-B granular halves
-    if ((rc = slk_ensure(ctx, ctx->snap, (size_t)bsz * L * RS * 4))) return rc;
-    if ((rc = slk_ensure(ctx, ctx->extra[SQ_GSN], (size_t)bsz * L * NP * 4))) return rc;  // dL/dscore per (timestep, pair)
-    const unsigned max_grid = (unsigned)ctx->num_cus * 8;
-    if ((rc = slk_ensure(ctx, ctx->losspart, (size_t)max_grid * 8))) return rc;
-    const bool dense = slk_opt_is_dense(optim->kind);
-    if (dense) {
-        const size_t elems[4] = {0, (size_t)(Hi ? ibd.rows : tables->num_items) * D, 0, (size_t)tables->num_items};
-        if ((rc = slk_ensure_dgrad(ctx, elems, TM, s))) return rc;
-    }
-    const int upd = slk_upd_for(optim->kind);
-    seq_pass_fn spass = nullptr;
-    slk_item_fns ipass = {nullptr, nullptr}, ipass_rows = ipass, ipass_bias = ipass;
-    // register-resident sequence pass when a group's chunk of timesteps fits 16 rows of VGPRs
-    const bool reg_pass = L <= 256 && (L + NG - 1) / NG <= 16 && ctx->opt_seq_variant != 0;
+    if ((rc = slk_ensure(ctx, ctx->snap, (size_t)p.bsz * p.L * p.RS * 4))) return rc;
+    if ((rc = slk_ensure(ctx, ctx->extra[SQ_GSN], (size_t)p.bsz * p.L * NP * 4))) return rc;  // dL/dscore per (timestep, pair)
+    if ((rc = slk_ensure(ctx, ctx->losspart, (size_t)p.max_grid * 8))) return rc;
+    if (p.dense && (rc = slk_ensure_dgrad(ctx, p.dense_elems, SEQ_TABLES, s))) return rc;
+    return SLK_OK;
+}
+
+static int pick_seq_kernels(slk_ctx *ctx, const seq_plan &p, const slk_optim *optim, seq_kernels *kernels) {
+    seq_kernels &k = *kernels;
+    const int upd = slk_upd_for(optim->kind), Hi = p.Hi;
+    const bool reg_pass = p.reg_pass, adaptive = p.adaptive;
+    k = seq_kernels{};
 #define SLK_PICK(V_, G_)                                                                 \
     do {                                                                                 \
         constexpr int CM_ = (G_) < 16 ? (G_) : 16;                                       \
         if (reg_pass && Hi)                                                              \
-            spass = adaptive ? k_seq_pass_reg<V_, G_, true, true, CM_> : k_seq_pass_reg<V_, G_, false, true, CM_>; \
+            k.spass = adaptive ? k_seq_pass_reg<V_, G_, true, true, CM_> : k_seq_pass_reg<V_, G_, false, true, CM_>; \
         else if (reg_pass)                                                               \
-            spass = adaptive ? k_seq_pass_reg<V_, G_, true, false, CM_> : k_seq_pass_reg<V_, G_, false, false, CM_>; \
+            k.spass = adaptive ? k_seq_pass_reg<V_, G_, true, false, CM_> : k_seq_pass_reg<V_, G_, false, false, CM_>; \
         else if (Hi)                                                                     \
-            spass = adaptive ? k_seq_pass<V_, G_, true, true> : k_seq_pass<V_, G_, false, true>; \
+            k.spass = adaptive ? k_seq_pass<V_, G_, true, true> : k_seq_pass<V_, G_, false, true>; \
         else                                                                             \
-            spass = adaptive ? k_seq_pass<V_, G_, true, false> : k_seq_pass<V_, G_, false, false>; \
-        ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ>(upd);                             \
+            k.spass = adaptive ? k_seq_pass<V_, G_, true, false> : k_seq_pass<V_, G_, false, false>; \
+        k.ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ>(upd);                           \
         if (Hi) {                                                                        \
-            ipass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ, SLK_PART_ROWS>(upd);     \
-            ipass_bias = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ, SLK_PART_BIAS>(upd);     \
+            k.ipass_rows = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ, SLK_PART_ROWS>(upd);   \
+            k.ipass_bias = slk_item_pass_fn<V_, G_, SLK_ITEM_SEQ, SLK_PART_BIAS>(upd);   \
         }                                                                                \
     } while (0)
-    SLK_FOR_LAYOUT(vec, g, SLK_PICK);
+    SLK_FOR_LAYOUT(p.vec, p.g, SLK_PICK);
 #undef SLK_PICK
-    if (!reg_pass && lds_bytes > 48 * 1024)
-        SLK_HIP(ctx, hipFuncSetAttribute((const void *)spass, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes));
-    const unsigned gpb = 256u / (unsigned)g;
+    if (!reg_pass && p.lds_bytes > 48 * 1024)
+        SLK_HIP(ctx, hipFuncSetAttribute((const void *)k.spass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    return SLK_OK;
+}
 
-    if (reserve_only) {
-        if (nsets == 2 && (rc = slk_prep_stream_init(ctx))) return rc;
-        for (int st = 0; st < nsets; ++st) {  // pinned read-back buffers + events of the long-run flags (slk_bilinear.hip)
-            slk_prep_bufs &pb = ctx->pb[st];
-            if ((rc = slk_ensure_lflags_host(ctx, pb, (size_t)mb_per_chunk))) return rc;
-            pb.h_lflags_n = 0;
-            if (!pb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&pb.ev_lflags, hipEventDisableTiming));
-        }
-        // sampler and sort scratch of the largest chunk, so that the training call allocates nothing
-        if ((rc = slk_sample_reserve(ctx, tables->num_items, (int64_t)nts_max * nn))) return rc;
-        return slk_sort_reserve(ctx, nts_max * (size_t)occ_mult);
+// slk_poolnet_reserve: what a training call of this plan would otherwise allocate or set up on its way
+static int reserve_seq_extras(slk_ctx *ctx, const seq_plan &p, const seq_call &c) {
+    int rc;
+    if (p.nsets == 2 && (rc = slk_prep_stream_init(ctx))) return rc;
+    for (int st = 0; st < p.nsets; ++st)
+        if ((rc = slk_lflags_reserve(ctx, ctx->pb[st], (size_t)p.mb_per_chunk))) return rc;
+    // sampler and sort scratch of the largest chunk, so that the training call allocates nothing
+    if ((rc = slk_sample_reserve(ctx, c.tables->num_items, (int64_t)p.nts_max * p.nn))) return rc;
+    return slk_sort_reserve(ctx, p.nts_max * (size_t)p.occ_mult);
+}
+
+// ---- prep of one chunk into buffer set `pb` (value-independent: ids only), in two halves: the negatives, then the mask
+// counts, the sorts and the long-run flags
+static int seq_prep_sample(slk_ctx *ctx, const seq_plan &p, const seq_call &c, int64_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    // one randint per minibatch == one contiguous draw over the chunk
+    const int64_t n0 = chunk_begin(p, ck) * p.L * p.nn;
+    const size_t nneg = (size_t)(chunk_len(p, c, ck) * (uint32_t)p.L) * p.nn;
+    if (c.neg_in) return slk_prep_given_negatives(ctx, c.neg_in + n0, c.neg_out ? c.neg_out + n0 : nullptr, nneg, pb, s);
+    return slk_sample_u32(ctx, c.tables->num_items, (int64_t)nneg, (uint32_t *)pb.neg32.p, c.neg_out ? c.neg_out + n0 : nullptr, s);
+}
+
+static int seq_prep_sort(slk_ctx *ctx, const seq_plan &p, const seq_call &c, int64_t ck, slk_prep_bufs &pb, hipStream_t s) {
+    int rc;
+    const uint32_t ns = chunk_len(p, c, ck), L = (uint32_t)p.L, NP = (uint32_t)p.NP, bsz = (uint32_t)p.bsz;
+    const uint32_t nocc = ns * L * NP;
+    const uint32_t n_mb = (uint32_t)((ns + p.bsz - 1) / p.bsz);
+    const int64_t *cs = c.sequences + chunk_begin(p, ck) * p.L;
+    const uint32_t *neg32 = (const uint32_t *)pb.neg32.p;
+    const int Hi = p.Hi;
+    // ---- prep: mask counts; occurrences sorted by (minibatch, item)
+    slk_prof_begin(ctx, SLK_K_PREP, s);
+    SLK_HIP(ctx, hipMemsetAsync(pb.mcount.p, 0, (size_t)n_mb * 4, s));
+    {
+        unsigned gx = (unsigned)(((size_t)p.bsz * p.L + 8191) / 8192);
+        if (gx > 256) gx = 256;
+        hipLaunchKernelGGL(k_seq_count, dim3(gx, n_mb), dim3(256), 0, s, cs, ns, L, bsz, (uint32_t *)pb.mcount.p);
+        SLK_LAUNCH_CHECK(ctx, "k_seq_count");
     }
-    int64_t mb_global = 0;
-    // ---- prep of the chunk starting at sequence c0 into buffer set `set`, on stream s (ids only: value-independent)
-    auto do_prep = [&](int64_t c0, int set, hipStream_t s) -> int {
-        int rc;
-        slk_prep_bufs &fb = ctx->pb[set];
-        const uint32_t ns = (uint32_t)((n_seq - c0 < chunk_seqs) ? (n_seq - c0) : chunk_seqs);
-        const uint32_t nts = ns * (uint32_t)L;
-        const uint32_t nocc = nts * (uint32_t)NP;
-        const int64_t *cs = d_sequences + c0 * L;
-        uint32_t *neg32 = (uint32_t *)fb.neg32.p;
-        const uint32_t n_mb = (uint32_t)((ns + bsz - 1) / bsz);
-        // ---- negatives: one randint per minibatch == one contiguous draw over the chunk
-        if (d_neg_in) {
-            slk_prof_begin(ctx, SLK_K_SAMPLE, s);
-            if ((rc = slk_launch_i64_to_u32(ctx, d_neg_in + c0 * L * nn, neg32, (size_t)nts * nn, s))) return rc;
-            if (d_neg_out)
-                SLK_HIP(ctx, hipMemcpyAsync(d_neg_out + c0 * L * nn, d_neg_in + c0 * L * nn, (size_t)nts * nn * 8,
-                                            hipMemcpyDeviceToDevice, s));
-            slk_prof_end(ctx, s);
-        } else {
-            if ((rc = slk_sample_u32(ctx, tables->num_items, (int64_t)nts * nn, neg32,
-                                     d_neg_out ? d_neg_out + c0 * L * nn : nullptr, s)))
-                return rc;
-        }
-        // ---- prep: mask counts; occurrences sorted by (minibatch, item)
-        slk_prof_begin(ctx, SLK_K_PREP, s);
-        uint32_t *mcount = (uint32_t *)ctx->extra[set ? SQ_MCOUNT_B : SQ_MCOUNT].p;
-        SLK_HIP(ctx, hipMemsetAsync(mcount, 0, (size_t)n_mb * 4, s));
-        {
-            unsigned gx = (unsigned)(((size_t)bsz * L + 8191) / 8192);
-            if (gx > 256) gx = 256;
-            hipLaunchKernelGGL(k_seq_count, dim3(gx, n_mb), dim3(256), 0, s, cs, ns, (uint32_t)L, (uint32_t)bsz,
-                               mcount);
-            SLK_LAUNCH_CHECK(ctx, "k_seq_count");
-        }
-        const unsigned mbbits = slk_bits_for((uint64_t)(n_mb - 1));
-        hipLaunchKernelGGL(k_seq_item_keys, dim3(slk_grid_for(ctx, nocc, 256)), dim3(256), 0, s, cs,
-                           (const uint32_t *)neg32, nocc, ns, (uint32_t)L, (uint32_t)NP, (uint32_t)bsz, ibits,
-                           (uint32_t *)fb.ikey[0].p, (uint32_t *)fb.ipay[0].p);
-        SLK_LAUNCH_CHECK(ctx, "k_seq_item_keys");
-        if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)fb.ikey[0].p, (uint32_t *)fb.ikey[1].p,
-                                         (const uint32_t *)fb.ipay[0].p, (uint32_t *)fb.ipay[1].p, nocc,
-                                         ibits + mbbits, s, true)))
+    const unsigned mbbits = slk_bits_for((uint64_t)(n_mb - 1));
+    hipLaunchKernelGGL(k_seq_item_keys, dim3(slk_grid_for(ctx, nocc, 256)), dim3(256), 0, s, cs, neg32, nocc, ns, L, NP, bsz,
+                       p.ibits, (uint32_t *)pb.ikey[0].p, (uint32_t *)pb.ipay[0].p);
+    SLK_LAUNCH_CHECK(ctx, "k_seq_item_keys");
+    if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)pb.ikey[0].p, (uint32_t *)pb.ikey[1].p, (const uint32_t *)pb.ipay[0].p,
+                                     (uint32_t *)pb.ipay[1].p, nocc, p.ibits + mbbits, s, true)))
+        return rc;
+    // which minibatches hold a LONG run of the plain occurrence list (slk_kernels.h, k_item_long_flags): fetched once
+    // per chunk; the usual minibatch (none) gets the plain item pass with no stitch kernel behind it
+    if ((rc = slk_ensure(ctx, pb.lflags, (size_t)n_mb * 4))) return rc;
+    SLK_HIP(ctx, hipMemsetAsync(pb.lflags.p, 0, (size_t)n_mb * 4, s));
+    hipLaunchKernelGGL(k_item_long_flags, dim3(slk_grid_for(ctx, nocc / (4 * p.gpb) + n_mb, 256)), dim3(256), 0, s,
+                       (const uint32_t *)pb.ikey[1].p, nocc, bsz * L * NP, 4u * p.gpb, (uint32_t)((1ull << p.ibits) - 1),
+                       c.padding_idx < 0 ? 0xffffffffu : (uint32_t)c.padding_idx, 0xffffffffu, (int *)pb.lflags.p);
+    SLK_LAUNCH_CHECK(ctx, "k_item_long_flags");
+    if ((rc = slk_lflags_readback(ctx, pb, n_mb, s))) return rc;
+    if (Hi) {
+        hipLaunchKernelGGL(k_seq_item_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nocc * Hi, 256)), dim3(256), 0, s, cs, neg32, nocc,
+                           ns, L, NP, bsz, p.icbits, p.ibd, (uint32_t *)pb.bik[0].p, (uint32_t *)pb.bip[0].p);
+        SLK_LAUNCH_CHECK(ctx, "k_seq_item_bloom_keys");
+        if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)pb.bik[0].p, (uint32_t *)pb.bik[1].p, (const uint32_t *)pb.bip[0].p,
+                                         (uint32_t *)pb.bip[1].p, (size_t)nocc * Hi, p.icbits + mbbits, s, true)))
             return rc;
-        // which minibatches hold a LONG run of the plain occurrence list (slk_kernels.h, k_item_long_flags): fetched once
-        // per chunk; the usual minibatch (none) gets the plain item pass with no stitch kernel behind it
-        if ((rc = slk_ensure(ctx, fb.lflags, (size_t)n_mb * 4))) return rc;
-        SLK_HIP(ctx, hipMemsetAsync(fb.lflags.p, 0, (size_t)n_mb * 4, s));
-        hipLaunchKernelGGL(k_item_long_flags, dim3(slk_grid_for(ctx, nocc / (4 * gpb) + n_mb, 256)), dim3(256), 0, s,
-                           (const uint32_t *)fb.ikey[1].p, nocc, (uint32_t)bsz * (uint32_t)L * (uint32_t)NP, 4u * gpb,
-                           (uint32_t)((1ull << ibits) - 1), padding_idx < 0 ? 0xffffffffu : (uint32_t)padding_idx, 0xffffffffu,
-                           (int *)fb.lflags.p);
-        SLK_LAUNCH_CHECK(ctx, "k_item_long_flags");
-        if ((rc = slk_ensure_lflags_host(ctx, fb, n_mb))) return rc;
-        SLK_HIP(ctx, hipMemcpyAsync(fb.h_lflags, fb.lflags.p, (size_t)n_mb * 4, hipMemcpyDeviceToHost, s));
-        if (!fb.ev_lflags) SLK_HIP(ctx, hipEventCreateWithFlags(&fb.ev_lflags, hipEventDisableTiming));
-        SLK_HIP(ctx, hipEventRecord(fb.ev_lflags, s));
-        if (Hi) {
-            hipLaunchKernelGGL(k_seq_item_bloom_keys, dim3(slk_grid_for(ctx, (size_t)nocc * Hi, 256)), dim3(256), 0, s, cs,
-                               (const uint32_t *)neg32, nocc, ns, (uint32_t)L, (uint32_t)NP, (uint32_t)bsz, icbits, ibd,
-                               (uint32_t *)fb.bik[0].p, (uint32_t *)fb.bip[0].p);
-            SLK_LAUNCH_CHECK(ctx, "k_seq_item_bloom_keys");
-            if ((rc = slk_sort_pairs_u32_u32(ctx, (const uint32_t *)fb.bik[0].p,
-                                             (uint32_t *)fb.bik[1].p,
-                                             (const uint32_t *)fb.bip[0].p,
-                                             (uint32_t *)fb.bip[1].p, (size_t)nocc * Hi, icbits + mbbits, s, true)))
-                return rc;
-        }
-        slk_prof_end(ctx, s);
-        return SLK_OK;
-    };
-
-    // ---- the minibatches of one prepared chunk, in order, on the caller's stream
-    auto do_passes = [&](int64_t c0, int set) -> int {
-        int rc;
-        slk_prep_bufs &fb = ctx->pb[set];
-        const uint32_t ns = (uint32_t)((n_seq - c0 < chunk_seqs) ? (n_seq - c0) : chunk_seqs);
-        const int64_t *cs = d_sequences + c0 * L;
-        uint32_t *neg32 = (uint32_t *)fb.neg32.p;
-        uint32_t *mcount = (uint32_t *)ctx->extra[set ? SQ_MCOUNT_B : SQ_MCOUNT].p;
-        bool lflags_ready = false;
-        for (uint32_t b0 = 0, mb = 0; b0 < ns; b0 += (uint32_t)bsz, ++mb, ++mb_global) {
-            const uint32_t b1 = (ns - b0 < (uint32_t)bsz) ? ns : b0 + (uint32_t)bsz;
-            slk_seq_args q;
-            memset(&q, 0, sizeof(q));
-            q.E = tables->d_param[1];
-            q.bias = tables->d_param[3];
-            q.D = D;
-            q.L = (int)L;
-            q.NP = NP;
-            q.seqs = cs;
-            q.neg32 = neg32 + (size_t)b0 * nn * L;
-            q.s_begin = b0;
-            q.s_end = b1;
-            q.rec = (float *)ctx->snap.p;
-            q.RS = RS;
-            q.gsn = (float *)ctx->extra[SQ_GSN].p;
-            q.mcount = mcount + mb;
-            q.loss_partial = (double *)ctx->losspart.p;
-            q.loss_kind = loss;
-            q.C = (int)((L + NG - 1) / NG);
-            q.ib = ibd;
-            unsigned sgrid = b1 - b0;
-            if (sgrid > max_grid) sgrid = max_grid;
-            slk_prof_begin(ctx, SLK_K_SEQ_PASS, s);
-            hipLaunchKernelGGL(spass, dim3(sgrid), dim3(256), reg_pass ? 0 : lds_bytes, s, q);
-            SLK_LAUNCH_CHECK(ctx, "k_seq_pass");
-            slk_prof_end(ctx, s);
-
-            slk_pass_args a;
-            memset(&a, 0, sizeof(a));
-            for (int t = 0; t < 4; ++t) {
-                a.P[t] = tables->d_param[t];
-                a.S1[t] = dense ? (float *)ctx->dgrad[t].p : optim->d_state1[t];
-                a.S2[t] = optim->d_state2[t];
-            }
-            a.D = D;
-            a.NP = NP;
-            a.begin = b0 * (uint32_t)L;
-            a.end = b1 * (uint32_t)L;
-            a.snap = (float *)ctx->snap.p;
-            a.RS = RS;
-            a.gsn = (float *)ctx->extra[SQ_GSN].p;
-            a.ibegin = a.begin * (uint32_t)NP;
-            a.iend = a.end * (uint32_t)NP;
-            a.ikey = (const uint32_t *)fb.ikey[1].p;
-            a.imask = (uint32_t)((1ull << ibits) - 1);
-            a.ipay = (const uint32_t *)fb.ipay[1].p;
-            a.pad_item = padding_idx < 0 ? 0xffffffffu : (uint32_t)padding_idx;
-            a.pad_item2 = 0xffffffffu;
-            a.loss_partial = (double *)ctx->losspart.p;
-            a.n_loss_partial = (int)sgrid;
-            a.mb_loss_out = d_mb_loss + mb_global;
-            a.loss_kind = loss;
-            a.inv_b = 1.0f;  // the sequence pass already divided its partials by mask.sum()
-            slk_set_opt_coeffs(a, optim);
-            a.nt = ctx->opt_nt;
-            if (!lflags_ready) {  // the chunk's first sequence pass is queued: the GPU is busy while the host waits
-                SLK_HIP(ctx, hipEventSynchronize(fb.ev_lflags));
-                lflags_ready = true;
-            }
-            const bool may_long = !ctx->opt_item_long_gate || fb.h_lflags[mb] != 0;
-            slk_prof_begin(ctx, SLK_K_ITEM_PASS, s);
-            if (!Hi) {
-                if ((rc = slk_launch_item_pass(ctx, ipass, a, g, s, "k_item_pass<SEQ>", may_long, 4))) return rc;
-            } else {
-                // item biases are indexed by the item id: plain occurrence list, bias only ...
-                if ((rc = slk_launch_item_pass(ctx, ipass_bias, a, g, s, "k_item_pass<SEQ,BIAS>", may_long, 4))) return rc;
-                // ... while every occurrence feeds the n_hash hashed rows of the compressed table
-                slk_pass_args r = a;
-                r.mb_loss_out = nullptr;
-                r.ikey = (const uint32_t *)fb.bik[1].p;
-                r.ipay = (const uint32_t *)fb.bip[1].p;
-                r.ibegin = a.ibegin * (uint32_t)Hi;
-                r.iend = a.iend * (uint32_t)Hi;
-                r.imask = (uint32_t)((1ull << icbits) - 1);
-                r.pad_item = tables->item_bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)tables->item_bloom->skip_row;
-                if ((rc = slk_launch_item_pass(ctx, ipass_rows, r, g, s, "k_item_pass<SEQ,ROWS>"))) return rc;
-            }
-            slk_prof_end(ctx, s);
-            if (dense && (rc = slk_dense_sweeps(ctx, tables->d_param, optim, TM, s))) return rc;
-            optim->step += 1;
-        }
-        return SLK_OK;
-    };
-
-    auto do_chunk = [&](int64_t c0, int set) -> int { return do_passes(c0, set); };
-
-    if (nsets == 1) {
-        for (int64_t c0 = 0; c0 < n_seq; c0 += chunk_seqs) {
-            if ((rc = do_prep(c0, 0, s))) return rc;
-            if ((rc = do_chunk(c0, 0))) return rc;
-        }
-        return SLK_OK;
     }
-    // pipeline: prep(c + 1) on ctx->prep_stream beside passes(c) on the caller's stream (slk_bilinear.hip)
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+// What every minibatch of chunk `ck` is handed: the sequence pass's arguments and the item pass's.
+struct seq_chunk_args {
+    slk_seq_args q;
+    slk_pass_args a;
+};
+
+static void seq_chunk_pass_args(slk_ctx *ctx, const seq_plan &p, const seq_call &c, int64_t ck, const slk_prep_bufs &pb,
+                                seq_chunk_args *args) {
+    slk_seq_args &q = args->q;
+    memset(&q, 0, sizeof(q));
+    q.E = c.tables->d_param[1];
+    q.bias = c.tables->d_param[3];
+    q.D = p.D;
+    q.L = (int)p.L;
+    q.NP = p.NP;
+    q.seqs = c.sequences + chunk_begin(p, ck) * p.L;
+    q.neg32 = (const uint32_t *)pb.neg32.p;  // (the chunk's; a minibatch reads from its own offset)
+    q.rec = (float *)ctx->snap.p;
+    q.RS = p.RS;
+    q.gsn = (float *)ctx->extra[SQ_GSN].p;
+    q.mcount = (const uint32_t *)pb.mcount.p;  // (likewise)
+    q.loss_partial = (double *)ctx->losspart.p;
+    q.loss_kind = c.loss;
+    q.C = (int)((p.L + p.NG - 1) / p.NG);
+    q.ib = p.ibd;
+    slk_pass_args &a = args->a;
+    memset(&a, 0, sizeof(a));
+    slk_fill_table_args(a, ctx, c.tables, c.optim, p.dense);
+    a.D = p.D;
+    a.NP = p.NP;
+    a.snap = (float *)ctx->snap.p;
+    a.RS = p.RS;
+    a.gsn = (float *)ctx->extra[SQ_GSN].p;
+    a.ikey = (const uint32_t *)pb.ikey[1].p;
+    a.imask = (uint32_t)((1ull << p.ibits) - 1);
+    a.ipay = (const uint32_t *)pb.ipay[1].p;
+    a.pad_item = c.padding_idx < 0 ? 0xffffffffu : (uint32_t)c.padding_idx;
+    a.pad_item2 = 0xffffffffu;
+    a.loss_partial = (double *)ctx->losspart.p;
+    a.loss_kind = c.loss;
+    a.inv_b = 1.0f;  // the sequence pass already divided its partials by mask.sum()
+    a.nt = ctx->opt_nt;
+}
+
+// the owner pass(es) of one minibatch's item rows
+static int item_stage(slk_ctx *ctx, const seq_plan &p, const seq_call &c, const seq_kernels &k, const slk_prep_bufs &pb,
+                      slk_pass_args &a, bool may_long, hipStream_t s) {
+    int rc;
+    slk_prof_begin(ctx, SLK_K_ITEM_PASS, s);
+    if (!p.Hi) {
+        if ((rc = slk_launch_item_pass(ctx, k.ipass, a, p.g, s, "k_item_pass<SEQ>", may_long, 4))) return rc;
+    } else {
+        // item biases are indexed by the item id: plain occurrence list, bias only ...
+        if ((rc = slk_launch_item_pass(ctx, k.ipass_bias, a, p.g, s, "k_item_pass<SEQ,BIAS>", may_long, 4))) return rc;
+        // ... while every occurrence feeds the n_hash hashed rows of the compressed table
+        const slk_bloom *bloom = c.tables->item_bloom;
+        slk_pass_args r = a;
+        r.mb_loss_out = nullptr;
+        r.ikey = (const uint32_t *)pb.bik[1].p;
+        r.ipay = (const uint32_t *)pb.bip[1].p;
+        r.ibegin = a.ibegin * (uint32_t)p.Hi;
+        r.iend = a.iend * (uint32_t)p.Hi;
+        r.imask = (uint32_t)((1ull << p.icbits) - 1);
+        r.pad_item = bloom->skip_row < 0 ? 0xffffffffu : (uint32_t)bloom->skip_row;
+        if ((rc = slk_launch_item_pass(ctx, k.ipass_rows, r, p.g, s, "k_item_pass<SEQ,ROWS>"))) return rc;
+    }
+    slk_prof_end(ctx, s);
+    return SLK_OK;
+}
+
+// ---- the minibatches of one prepared chunk, in order, on the caller's stream
+static int run_seq_passes(slk_ctx *ctx, const seq_plan &p, const seq_call &c, const seq_kernels &k, int64_t &mb_global, int64_t ck,
+                          slk_prep_bufs &pb, hipStream_t s) {
+    int rc;
+    const uint32_t ns = chunk_len(p, c, ck), bsz = (uint32_t)p.bsz, L = (uint32_t)p.L;
+    seq_chunk_args chunk;
+    seq_chunk_pass_args(ctx, p, c, ck, pb, &chunk);
+    for (uint32_t b0 = 0, mb = 0; b0 < ns; b0 += bsz, ++mb, ++mb_global) {
+        const uint32_t b1 = (ns - b0 < bsz) ? ns : b0 + bsz;
+        slk_seq_args q = chunk.q;
+        q.neg32 += (size_t)b0 * p.nn * p.L;
+        q.s_begin = b0;
+        q.s_end = b1;
+        q.mcount += mb;
+        unsigned sgrid = b1 - b0;
+        if (sgrid > p.max_grid) sgrid = p.max_grid;
+        slk_prof_begin(ctx, SLK_K_SEQ_PASS, s);
+        hipLaunchKernelGGL(k.spass, dim3(sgrid), dim3(256), p.reg_pass ? 0 : p.lds_bytes, s, q);
+        SLK_LAUNCH_CHECK(ctx, "k_seq_pass");
+        slk_prof_end(ctx, s);
+
+        slk_pass_args a = chunk.a;
+        a.begin = b0 * L;
+        a.end = b1 * L;
+        a.ibegin = a.begin * (uint32_t)p.NP;
+        a.iend = a.end * (uint32_t)p.NP;
+        a.n_loss_partial = (int)sgrid;
+        a.mb_loss_out = c.mb_loss + mb_global;
+        slk_set_opt_coeffs(a, c.optim);
+        // the chunk's long-run flags (seq_prep_sort): ONE host wait per chunk -- the chunk's first sequence pass is queued, the
+        // GPU is busy while the host waits
+        if (mb == 0) SLK_HIP(ctx, hipEventSynchronize(pb.ev_lflags));
+        const bool may_long = !ctx->opt_item_long_gate || pb.h_lflags[mb] != 0;
+        if ((rc = item_stage(ctx, p, c, k, pb, a, may_long, s))) return rc;
+        if (p.dense && (rc = slk_dense_sweeps(ctx, c.tables->d_param, c.optim, SEQ_TABLES, s))) return rc;
+        c.optim->step += 1;
+    }
+    return SLK_OK;
+}
+
+// every chunk in order on the caller's stream, through buffer set 0
+static int run_seq_inline(slk_ctx *ctx, const seq_plan &p, const seq_call &c, const seq_kernels &k, int64_t &mb_global) {
+    int rc;
+    for (int64_t ck = 0; ck < p.n_chunks; ++ck) {
+        if ((rc = seq_prep_sample(ctx, p, c, ck, ctx->pb[0], c.s))) return rc;
+        if ((rc = seq_prep_sort(ctx, p, c, ck, ctx->pb[0], c.s))) return rc;
+        if ((rc = run_seq_passes(ctx, p, c, k, mb_global, ck, ctx->pb[0], c.s))) return rc;
+    }
+    ctx->last_pipe_set = -1;  // what slk_bilinear_prefetch goes by: this call used buffer set 0 on the caller's stream
+    return SLK_OK;
+}
+
+// pipeline: prep(c + 1) on ctx->prep_stream beside passes(c) on the caller's stream
+static int run_seq_pipelined(slk_ctx *ctx, const seq_plan &p, const seq_call &c, const seq_kernels &k, int64_t &mb_global) {
+    int rc;
+    hipStream_t s = c.s;
     if ((rc = slk_prep_stream_init(ctx))) return rc;
     hipStream_t ps = ctx->prep_stream;
     SLK_HIP(ctx, hipEventRecord(ctx->ev_start, s));  // inputs produced on the caller's stream
     SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_start, 0));
-    if ((rc = do_prep(0, 0, ps))) return rc;
+    if ((rc = seq_prep_sample(ctx, p, c, 0, ctx->pb[0], ps))) return rc;
+    if ((rc = seq_prep_sort(ctx, p, c, 0, ctx->pb[0], ps))) return rc;
     SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[0], ps));
     int set = 0;
-    for (int64_t c0 = 0; c0 < n_seq; c0 += chunk_seqs, set ^= 1) {
+    for (int64_t ck = 0; ck < p.n_chunks; ++ck, set ^= 1) {
         SLK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_prep[set], 0));
-        if (c0 + chunk_seqs < n_seq) {
-            if (c0 > 0) SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[set ^ 1], 0));  // that set's last reader: the chunk before
-            if ((rc = do_prep(c0 + chunk_seqs, set ^ 1, ps))) return rc;
+        if (ck + 1 < p.n_chunks) {
+            if (ck > 0) SLK_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_done[set ^ 1], 0));  // that set's last reader: the chunk before
+            if ((rc = seq_prep_sample(ctx, p, c, ck + 1, ctx->pb[set ^ 1], ps))) return rc;
+            if ((rc = seq_prep_sort(ctx, p, c, ck + 1, ctx->pb[set ^ 1], ps))) return rc;
             SLK_HIP(ctx, hipEventRecord(ctx->ev_prep[set ^ 1], ps));
             ++ctx->stat_overlapped;
         }
-        if ((rc = do_chunk(c0, set))) return rc;
+        if ((rc = run_seq_passes(ctx, p, c, k, mb_global, ck, ctx->pb[set], s))) return rc;
         SLK_HIP(ctx, hipEventRecord(ctx->ev_done[set], s));
     }
+    ctx->last_pipe_set = set ^ 1;  // the set of the last chunk (the loop's last increment undone), as slk_bilinear_train leaves it
     ctx->last_stream = s;  // every prep is ordered before the tail of the caller's stream
     return SLK_OK;
+}
+
+static int run_seq_training(slk_ctx *ctx, const seq_call &c) {
+    if (!ctx) return SLK_EINVAL;
+    seq_plan p;
+    int rc;
+    if ((rc = plan_seq_training(ctx, c, &p))) return rc;
+    if (p.n_chunks == 0) return SLK_OK;
+    if ((rc = ensure_seq_scratch(ctx, p, c.s))) return rc;
+    seq_kernels k;
+    if ((rc = pick_seq_kernels(ctx, p, c.optim, &k))) return rc;
+    if (c.mode == seq_call::RESERVE) return reserve_seq_extras(ctx, p, c);
+    int64_t mb_global = 0;
+    return p.nsets == 1 ? run_seq_inline(ctx, p, c, k, mb_global) : run_seq_pipelined(ctx, p, c, k, mb_global);
 }
 
 SLK_EXPORT int slk_poolnet_predict(slk_ctx *ctx, const slk_tables *tables, const int64_t *d_sequence,

@@ -697,11 +697,7 @@ static slk_pass_fn shard_user_pass_fn(int upd) {
 
 static void fill_tables(slk_pass_args &a, slk_ctx *ctx, const slk_tables *local, const slk_optim *optim,
                         bool dense) {
-    for (int t = 0; t < 4; ++t) {
-        a.P[t] = local->d_param[t];
-        a.S1[t] = dense ? (float *)ctx->dgrad[t].p : optim->d_state1[t];
-        a.S2[t] = optim->d_state2[t];
-    }
+    slk_fill_table_args(a, ctx, local, optim, dense);
     a.D = local->dim;
     a.NP = 2;
     a.pad_item = a.pad_item2 = 0xffffffffu;

@@ -622,10 +622,12 @@ def check_seq_train_matches_oracle(be, loss, opt, D, I=31, N=40, L=9, B=16, nn=3
 
 
 def check_seq_chunking_is_bit_neutral(be, loss, opt, D, I=2000, N=300, L=24, B=32, nn=3, chunk=2048, overlap=1, bloom=0, seed=17,
-                                      option=None):
+                                      option=None, negs_in=False):
     """PoolNet training in ONE prep chunk against the same call cut into several chunks of `chunk` timesteps with the prep of
     chunk c + 1 (negatives, occurrence sort, flags) on the second stream while chunk c trains (slk_seq.hip: the pipeline of
-    slk_bilinear_train): losses, negatives, RNG state, tables and optimizer state bit for bit."""
+    slk_bilinear_train): losses, negatives, RNG state, tables and optimizer state bit for bit.
+    `negs_in`: both runs are HANDED the same negatives (d_neg_in) instead of drawing them: every chunk reads its own window of
+    them, d_neg_out echoes them and the RNG state stays where it was set."""
     eng = be.engine
     rs = np.random.RandomState(seed)
     seqs = make_sequences(rs, N, L, I, 0.3)
@@ -635,6 +637,7 @@ def check_seq_chunking_is_bit_neutral(be, loss, opt, D, I=2000, N=300, L=24, B=3
     state = np.random.RandomState(seed + 1).get_state()
     n_mb = (N + B - 1) // B
     n_draw = N * L * (nn if loss == 'adaptive_hinge' else 1)
+    given = np.random.RandomState(seed).randint(0, I, n_draw).astype(np.int64) if negs_in else None
     results = []
     for run_i, (chunk_i, overlap_i) in enumerate(((1 << 23, 0), (chunk, overlap))):
         eng.set_option('chunk_interactions', chunk_i)
@@ -648,10 +651,14 @@ def check_seq_chunking_is_bit_neutral(be, loss, opt, D, I=2000, N=300, L=24, B=3
             d_seqs = be.alloc(seqs)
             mb_loss = be.alloc(np.zeros(n_mb, dtype=np.float32))
             neg_out = be.alloc(np.full(n_draw, -1, dtype=np.int64))
+            d_neg_in = be.alloc(given) if negs_in else None
             for _ in range(2):
                 eng.poolnet_train(dev.tables, dev.optim, 0, be.ptr(d_seqs), N, L, B, loss, nn, be.ptr(mb_loss),
-                                  d_neg_out=be.ptr(neg_out), stream=be.stream)
+                                  d_neg_in=be.ptr(d_neg_in), d_neg_out=be.ptr(neg_out), stream=be.stream)
             st = eng.rng_get_state()
+            if negs_in:
+                assert np.array_equal(be.get(neg_out), given), 'd_neg_out is not the negatives the call was handed'
+                assert np.array_equal(st[1], state[1]) and st[2] == state[2], 'a call that was handed its negatives moved the RNG'
             results.append([be.get(mb_loss), be.get(neg_out), st[1], np.array(st[2])] + [be.get(x) for x in dev.p + dev.s1 + dev.s2])
         finally:
             eng.set_option('chunk_interactions', 1 << 23)
@@ -661,6 +668,174 @@ def check_seq_chunking_is_bit_neutral(be, loss, opt, D, I=2000, N=300, L=24, B=3
                 eng.set_option(option[0], option[3])
     for k, (a, b) in enumerate(zip(*results)):
         assert np.array_equal(a, b), ('tensor %d differs between one chunk and the pipelined chunks' % k)
+
+
+def _seq_case(be, opt, D, I, N, L, bloom, seed):
+    """sequences, a fresh model and the RNG state of check_seq_chunking_is_bit_neutral's case"""
+    from oracle.oracle import bloom_desc
+    rs = np.random.RandomState(seed)
+    seqs = make_sequences(rs, N, L, I, 0.3)
+    params = _seq_params(rs, I, D, rows=int(0.4 * I) if bloom else None)
+    dev = be.seq_model(params, opt=opt, item_bloom=bloom_desc(n_hash=bloom) if bloom else None, lr=0.05)
+    return seqs, dev, np.random.RandomState(seed + 1).get_state()
+
+
+def _seq_train_twice(be, dev, seqs, B, loss, nn):
+    """two training calls over `seqs`: [losses, negatives, RNG key, RNG position, tables, optimizer state]"""
+    eng = be.engine
+    N, L = seqs.shape
+    d_seqs = be.alloc(seqs)
+    mb_loss = be.alloc(np.zeros((N + B - 1) // B, dtype=np.float32))
+    neg_out = be.alloc(np.full(N * L * (nn if loss == 'adaptive_hinge' else 1), -1, dtype=np.int64))
+    for _ in range(2):
+        eng.poolnet_train(dev.tables, dev.optim, 0, be.ptr(d_seqs), N, L, B, loss, nn, be.ptr(mb_loss), d_neg_out=be.ptr(neg_out),
+                          stream=be.stream)
+    st = eng.rng_get_state()
+    return [be.get(mb_loss), be.get(neg_out), st[1], np.array(st[2])] + [be.get(x) for x in dev.p + dev.s1 + dev.s2]
+
+
+def check_seq_reserve_is_neutral(be, loss, opt, D, I=2000, N=300, L=24, B=32, nn=3, chunk=2048, overlap=1, seed=17):
+    """slk_poolnet_reserve only allocates: it leaves the RNG state, optim.step and the tables as they were, and the training calls
+    behind it give what they give without it, bit for bit."""
+    eng = be.engine
+    results = []
+    with eng.options(chunk_interactions=chunk, overlap_prep=overlap, overlap_min_batch=0):
+        for reserve in (True, False):
+            seqs, dev, state = _seq_case(be, opt, D, I, N, L, 0, seed)
+            eng.rng_set_state(state)
+            if reserve:
+                before = [be.get(x).copy() for x in dev.p + dev.s1 + dev.s2]
+                eng.poolnet_reserve(dev.tables, dev.optim, N, L, B, loss, nn, stream=be.stream)
+                st = eng.rng_get_state()
+                assert np.array_equal(st[1], state[1]) and st[2] == state[2], 'slk_poolnet_reserve moved the RNG'
+                assert dev.optim.step == 0
+                for k, (a, b) in enumerate(zip(before, [be.get(x) for x in dev.p + dev.s1 + dev.s2])):
+                    assert np.array_equal(a, b), 'slk_poolnet_reserve changed tensor %d' % k
+            results.append(_seq_train_twice(be, dev, seqs, B, loss, nn))
+    for k, (a, b) in enumerate(zip(*results)):
+        assert np.array_equal(a, b), 'tensor %d differs between training behind a reserve and training alone' % k
+
+
+# slk_poolnet_train's refusals: (what, arguments that differ from a good call, text of the error), in the order the rules are
+# checked in.  A good call: 2 sequences of 4 over 5 items at dim 8, minibatches of 2, bpr.  `ptr`: the case is one of a pointer
+# or of padding_idx, which slk_poolnet_reserve does not take.
+SEQ_REFUSALS = [
+    ('warp', dict(loss='warp'), 'slk_poolnet_train: warp (loss kind 7) is not built for the sequence model', False),
+    ('loss kind above the range', dict(loss=8), 'unknown loss kind 8', False),
+    ('loss kind below the range', dict(loss=-1), 'unknown loss kind -1', False),
+    ('adaptive hinge, no negatives', dict(loss='adaptive_hinge', n_neg=0), 'num_negative_samples 0 outside [1, 1024]', False),
+    ('adaptive hinge, 1025 negatives', dict(loss='adaptive_hinge', n_neg=1025), 'num_negative_samples 1025 outside [1, 1024]', False),
+    ('padding_idx == num_items', dict(padding_idx=5), 'padding_idx 5 outside [-1, num_items)', True),
+    ('padding_idx -2', dict(padding_idx=-2), 'padding_idx -2 outside [-1, num_items)', True),
+    ('seq_len 0', dict(seq_len=0), 'slk_poolnet_train: n_seq 2 batch_size 2 seq_len 0', False),
+    ('batch_size 0', dict(batch_size=0), 'slk_poolnet_train: n_seq 2 batch_size 0 seq_len 4', False),
+    ('n_seq < 0', dict(n_seq=-1), 'slk_poolnet_train: n_seq -1 batch_size 2 seq_len 4', False),
+    ('NULL d_sequences', dict(seqs=None), 'slk_poolnet_train: NULL pointer', True),
+    ('LDS bound', dict(seq_len=100000), 'sequence length 100000 x dim 8 does not fit the 160 KB LDS of a CU', False),
+    ('2^31 lookups per minibatch', dict(n_seq=1 << 28, batch_size=1 << 28), 'batch_size * seq_len * lookups per timestep must be < 2^31', False),
+    # where a call breaks two rules, the first one answers
+    ('warp and a bad padding_idx', dict(loss='warp', padding_idx=5), 'slk_poolnet_train: warp (loss kind 7)', True),
+    ('bad padding_idx and NULL pointers', dict(padding_idx=5, seqs=None, mb_loss=None), 'padding_idx 5 outside [-1, num_items)', True),
+]
+
+
+def check_seq_refusals(be):
+    """Every refusal of slk_poolnet_train, by its text (SEQ_REFUSALS); an empty call with NULL pointers succeeds; and
+    slk_poolnet_reserve refuses what it can be asked with the same code and the same text."""
+    from spotlight_amd import _native
+    eng = be.engine
+    dev = be.seq_model([np.zeros((5, 8)), np.zeros(5)])
+    seqs = be.alloc(np.zeros((2, 4), dtype=np.int64))
+    mb_loss = be.alloc(np.zeros(1, dtype=np.float32))
+
+    def refusal(call, *args, **kwargs):
+        try:
+            call(*args, **kwargs)
+        except _native.SlkError as e:
+            return e.code, str(e)
+        return None
+
+    for what, change, text, ptr in SEQ_REFUSALS:
+        a = dict(padding_idx=0, seqs=seqs, n_seq=2, seq_len=4, batch_size=2, loss='bpr', n_neg=1, mb_loss=mb_loss)
+        a.update(change)
+        got = refusal(eng.poolnet_train, dev.tables, dev.optim, a['padding_idx'], be.ptr(a['seqs']), a['n_seq'], a['seq_len'],
+                      a['batch_size'], a['loss'], a['n_neg'], be.ptr(a['mb_loss']), stream=be.stream)
+        assert got is not None, 'slk_poolnet_train accepted: ' + what
+        assert got[0] == _native.SLK_EINVAL and text in got[1], (what, got)
+        if not ptr:
+            again = refusal(eng.poolnet_reserve, dev.tables, dev.optim, a['n_seq'], a['seq_len'], a['batch_size'], a['loss'], a['n_neg'],
+                            stream=be.stream)
+            assert again == got, (what, again, got)
+    assert dev.optim.step == 0
+    eng.poolnet_train(dev.tables, dev.optim, 0, None, 0, 4, 2, 'bpr', 1, None, stream=be.stream)  # nothing to do: no pointer is read
+    assert dev.optim.step == 0
+
+
+def check_seq_route_that_was_meant_ran(be, D=16, I=2000, N=300, L=24, B=32, chunk=2048, seed=17):
+    """The 5 chunks of check_seq_chunking_is_bit_neutral's call: with "overlap_prep" 1 the prep of 4 of them runs beside the chunk
+    before (the statistic counts them, call by call), with 0 none does; either way the call launches the same kernels, class by
+    class."""
+    eng = be.engine
+    launches = []
+    for overlap, rise in ((0, 0), (1, 4)):
+        with eng.options(chunk_interactions=chunk, overlap_prep=overlap, overlap_min_batch=0):
+            seqs, dev, state = _seq_case(be, 'adagrad', D, I, N, L, 0, seed)
+            eng.rng_set_state(state)
+            d_seqs = be.alloc(seqs)
+            mb_loss = be.alloc(np.zeros((N + B - 1) // B, dtype=np.float32))
+            eng.profile_reset()
+            eng.profile_enable(True)
+            try:
+                for _ in range(2):
+                    before = eng.get_stat('overlapped_chunks')
+                    eng.poolnet_train(dev.tables, dev.optim, 0, be.ptr(d_seqs), N, L, B, 'bpr', 1, be.ptr(mb_loss), stream=be.stream)
+                    assert eng.get_stat('overlapped_chunks') - before == rise, (overlap, eng.get_stat('overlapped_chunks') - before)
+                launches.append({name: n for name, (n, _) in eng.profile_read().items()})
+            finally:
+                eng.profile_enable(False)
+                eng.profile_reset()
+    assert launches[0] == launches[1], launches
+    assert launches[0]['seq_pass'] == 2 * ((N + B - 1) // B)
+
+
+def check_bilinear_prefetch_behind_a_seq_call(be, D=8, U=60, I=50, N=700, B=128, chunk=256, seed=37):
+    """Both training drivers leave the ctx's record of the last pipelined buffer set in the same way, so a
+    slk_bilinear_prefetch behind a sequence call -- pipelined or in line -- knows which set it may overwrite: the prefetched
+    bilinear call (3 chunks) gives what it gives on a fresh engine, bit for bit.  (Values only: an ordering fault between the
+    two streams would not show here.)"""
+    rs = np.random.RandomState(seed)
+    users, items = rs.randint(0, U, N).astype(np.int64), rs.randint(0, I, N).astype(np.int64)
+    params = [rs.normal(0, 0.1, (U, D)), rs.normal(0, 0.1, (I, D)), np.zeros(U), np.zeros(I)]
+    state = np.random.RandomState(seed + 1).get_state()
+
+    def bilinear(be):
+        eng = be.engine
+        with eng.options(chunk_interactions=chunk, overlap_prep=1, overlap_min_batch=0, epoch_kernel=0):
+            dev = be.model(params, opt='adagrad', lr=0.05)
+            d_users, d_items = be.alloc(users), be.alloc(items)
+            mb_loss = be.alloc(np.zeros((N + B - 1) // B, dtype=np.float32))
+            neg_out = be.alloc(np.full(N, -1, dtype=np.int64))
+            eng.rng_set_state(state)
+            eng.bilinear_prefetch(dev.tables, dev.optim, be.ptr(d_users), be.ptr(d_items), N, B, 'bpr', 1, stream=be.stream)
+            assert eng.get_stat('prefetch_pending') > 0
+            eng.bilinear_train(dev.tables, dev.optim, be.ptr(d_users), be.ptr(d_items), N, B, 'bpr', 1, be.ptr(mb_loss),
+                               d_neg_out=be.ptr(neg_out), stream=be.stream)
+            st = eng.rng_get_state()
+            return [be.get(mb_loss), be.get(neg_out), st[1], np.array(st[2])] + [be.get(x) for x in dev.p + dev.s1]
+
+    fresh = type(be)()
+    try:
+        want = bilinear(fresh)
+    finally:
+        fresh.close()
+    for seq_overlap in (1, 0):
+        with be.engine.options(chunk_interactions=2048, overlap_prep=seq_overlap, overlap_min_batch=0):
+            seqs, dev, seq_state = _seq_case(be, 'adagrad', 16, 2000, 300, 24, 0, 17)
+            be.engine.rng_set_state(seq_state)
+            _seq_train_twice(be, dev, seqs, 32, 'bpr', 1)
+        for k, (a, b) in enumerate(zip(bilinear(be), want)):
+            assert np.array_equal(a, b), ('tensor %d of a prefetched bilinear call differs behind a sequence call (overlap_prep %d)'
+                                          % (k, seq_overlap))
 
 
 def check_seq_single_step_gradients(be, loss, D, I=40, B=24, L=11, nn=3, seed=11, bloom=0, ratio=0.4, tol=1e-5):

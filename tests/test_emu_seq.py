@@ -102,3 +102,30 @@ def test_seq_pass_forms_are_bit_identical(be, loss, opt, bloom):
 def test_seq_chunked_and_pipelined_prep_is_bit_neutral(be, loss, opt, bloom, overlap):
     """PoolNet: several prep chunks per call, in line and with the next chunk's prep on the second stream"""
     ec.check_seq_chunking_is_bit_neutral(be, loss, opt, 16, bloom=bloom, overlap=overlap)
+
+
+@pytest.mark.parametrize('loss,opt,bloom', [('bpr', 'adagrad', 0), ('adaptive_hinge', 'sparse_adam', 0), ('bpr', 'adagrad', 4)])
+@pytest.mark.parametrize('overlap', [0, 1])
+def test_seq_handed_in_negatives_across_chunks(be, loss, opt, bloom, overlap):
+    """PoolNet: the call is handed its negatives; 5 chunks, the last one a full and a short minibatch"""
+    ec.check_seq_chunking_is_bit_neutral(be, loss, opt, 16, bloom=bloom, overlap=overlap, negs_in=True)
+
+
+@pytest.mark.parametrize('shape', [dict(), dict(N=40, L=9, B=16, I=31, D=8, chunk=1 << 23)], ids=['chunks', 'one_chunk'])
+@pytest.mark.parametrize('overlap', [0, 1])
+def test_seq_reserve_is_neutral(be, shape, overlap):
+    shape = dict(dict(D=16), **shape)
+    ec.check_seq_reserve_is_neutral(be, 'bpr', 'adagrad', overlap=overlap, **shape)
+    ec.check_seq_reserve_is_neutral(be, 'adaptive_hinge', 'adam_dense', overlap=overlap, **shape)
+
+
+def test_seq_refusals_in_order(be):
+    ec.check_seq_refusals(be)
+
+
+def test_seq_route_that_was_meant_ran(be):
+    ec.check_seq_route_that_was_meant_ran(be)
+
+
+def test_bilinear_prefetch_behind_a_seq_call(be):
+    ec.check_bilinear_prefetch_behind_a_seq_call(be)

@@ -429,6 +429,33 @@ def test_seq_chunked_and_pipelined_prep_is_bit_neutral(be, loss, opt, bloom, ove
     ec.check_seq_chunking_is_bit_neutral(be, loss, opt, 16, bloom=bloom, overlap=overlap)
 
 
+@pytest.mark.parametrize('loss,opt,bloom', [('bpr', 'adagrad', 0), ('adaptive_hinge', 'sparse_adam', 0), ('bpr', 'adagrad', 4)])
+@pytest.mark.parametrize('overlap', [0, 1])
+def test_seq_handed_in_negatives_across_chunks(be, loss, opt, bloom, overlap):
+    """PoolNet: the call is handed its negatives; 5 chunks, the last one a full and a short minibatch"""
+    ec.check_seq_chunking_is_bit_neutral(be, loss, opt, 16, bloom=bloom, overlap=overlap, negs_in=True)
+
+
+@pytest.mark.parametrize('shape', [dict(), dict(N=40, L=9, B=16, I=31, D=8, chunk=1 << 23)], ids=['chunks', 'one_chunk'])
+@pytest.mark.parametrize('overlap', [0, 1])
+def test_seq_reserve_is_neutral(be, shape, overlap):
+    shape = dict(dict(D=16), **shape)
+    ec.check_seq_reserve_is_neutral(be, 'bpr', 'adagrad', overlap=overlap, **shape)
+    ec.check_seq_reserve_is_neutral(be, 'adaptive_hinge', 'adam_dense', overlap=overlap, **shape)
+
+
+def test_seq_refusals_in_order(be):
+    ec.check_seq_refusals(be)
+
+
+def test_seq_route_that_was_meant_ran(be):
+    ec.check_seq_route_that_was_meant_ran(be)
+
+
+def test_bilinear_prefetch_behind_a_seq_call(be):
+    ec.check_bilinear_prefetch_behind_a_seq_call(be)
+
+
 @pytest.mark.parametrize('D,U,B', [(64, 3, 1 << 16), (64, 50, 1 << 18), (32, 7, 40000), (128, 2, 30000), (64, 2000, 1 << 18)])
 def test_users_that_collect_thousands_of_occurrences(be, D, U, B):
     """hot users (VERDICT r02 missing 3): a user's occurrences fill hundreds to thousands of the user pass's 32-position tiles;
