@@ -66,7 +66,37 @@ enum slk_loss {
      * The rank estimate assumes uniform draws; under a weighted sampler it is a popularity-weighted rank.
      * Accepted by slk_bilinear_train / _reserve / _prefetch / _train_weighted and slk_bilinear_foldin (n_neg >= 1); the
      * explicit, sequence (PoolNet) and row-sharded entries refuse it with SLK_EINVAL. */
-    SLK_LOSS_WARP = 7
+    SLK_LOSS_WARP = 7,
+    /* SAMPLED SOFTMAX (InfoNCE; added to ABI 14: one new loss id, nothing existing changes, SLK_ABI_VERSION stays): the
+     * positive and ITS OWN n = n_neg draws in one softmax.  A MULTI-NEGATIVE loss like the column losses -- adaptive hinge's
+     * draws: one draw of bm * n values per minibatch of bm interactions, the generator ends where an adaptive-hinge call with
+     * the same n leaves it, d_neg_in / d_neg_out keep their meaning and layout -- but NOT a column loss: flat draw f of the
+     * minibatch is pair 1 + f % n of interaction f / n (the user it was drawn for; the storage's own layout), not row f / bm
+     * of column f % bm, and every one of the 1 + n pairs carries a gradient.  Per interaction k, with s_0 the positive's score
+     * and s_1 .. s_n the scores of pairs 1 .. n, in fp32:
+     *   m    = max_j s_j                          (fmaxf: a NaN is passed over here and caught by the next line)
+     *   e_j  = expf(s_j - m)
+     *   Zneg = e_1 + ... + e_n,   Z = e_0 + Zneg
+     *   l_k  = logf(Z) - (s_0 - m)
+     *   dL/ds_j = (e_j / Z) * inv_b  (j >= 1),   dL/ds_0 = -(Zneg / Z) * inv_b   (not (p_0 - 1): no cancellation as p_0 -> 1)
+     * ORDER, a function of n alone (not of the grid, bm, the chunking or the table kind; there is ONE form of the kernel):
+     * G = the smallest power of two >= min(n + 1, 64), at least 2; lane t of G holds pairs t, t + G, t + 2G, ... and folds
+     * them in that order, from -inf (max) and from 0.0f (sum; lane 0 leaves pair 0 out of the sum); the G lanes' values are
+     * then combined by the xor butterfly with masks G/2, G/4, ..., 1 (x = x + x_partner, fmaxf alike), which gives every lane
+     * the same bits; finally Z = e_0 + Zneg.
+     * USER BIAS: all 1 + n pairs of an interaction are one user's, so the user-bias gradient sum_j dL/ds_j is 0 in exact
+     * arithmetic.  Exactly 0.0f is applied -- not the 1e-9 residue of the fp32 sum, which Adagrad / Adam from a zero
+     * accumulator would turn into a step of lr (SparseAdam still decays the moments of the looked-up rows).
+     * minibatch loss = sum_k l_k / bm (the l_k summed in double).  With interaction weights (slk_bilinear_train_weighted)
+     * interaction k carries w_k on all of its 1 + n pairs: dL/ds_j = ((e_j / Z) * w_k) * inv_W, loss = sum(w_k l_k) / W;
+     * all-ones weights give the unweighted call's tables bit for bit.  A negative equal to the positive is not masked (as in
+     * every loss here); a NaN score makes every term of its interaction NaN.  No logQ correction under a weighted sampler.
+     * Accepted by slk_bilinear_train / _reserve / _prefetch / _train_weighted (1 <= n_neg <= 1024), always on the launch path
+     * (never the persistent kernel), over the chunk-sorted list of all 1 + n occurrences (plain and bloom tables); inside a
+     * user-row ping-pong scope refused as adaptive hinge is, inside an item-bias shadow scope trained as adaptive hinge is.
+     * The explicit, fold-in and row-sharded entries refuse it by name with SLK_EINVAL; the sequence (PoolNet) entries answer
+     * "unknown loss kind 8". */
+    SLK_LOSS_SOFTMAX = 8
 };
 
 /* Optimizers the reference can instantiate (factorization/implicit.py:143-150):
@@ -823,7 +853,7 @@ int slk_neighbors_scores(slk_ctx *ctx, const float *d_table, int64_t n_table_row
  *                       permutation of the users;
  *   step composition    one call with n_steps = T == T calls with n_steps = 1, the state carried in the caller's arrays.
  * Ids are NOT range-checked (as in slk_bilinear_train; spotlight_amd checks them on the host).  Refused with SLK_EINVAL: a NULL
- * required pointer, n_steps < 1, n_new_users < 1, n < 0, an explicit-feedback loss, n_neg < 1 under adaptive hinge or warp, a dim without
+ * required pointer, n_steps < 1, n_new_users < 1, n < 0, an explicit-feedback loss, softmax (by name), n_neg < 1 under adaptive hinge or warp, a dim without
  * a row layout, a bloom table on either side, item biases inside an open bias-shadow scope.  Nothing is retained, nothing is
  * allocated (no scratch at all), no host wait; profiled under SLK_K_USER_PASS. */
 int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_optim *optim, const int64_t *d_off, const int64_t *d_items,

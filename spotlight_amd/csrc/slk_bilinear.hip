@@ -375,6 +375,10 @@ __global__ __launch_bounds__(256) void k_user_pass(slk_pass_args a) {
                 break;
             }
         } while (true);
+        // sampled softmax: an interaction's 1 + n pairs are all this user's and their dL/dscore add up to 0 in exact arithmetic
+        // (-Zneg / Z + sum e_j / Z): the user-bias gradient IS zero.  The fp32 sum leaves a residue of 1e-9, which Adagrad and
+        // Adam from a zero accumulator turn into a step of lr -- the exact value is applied instead (include/spotlight_hip.h)
+        if (UMODE == 1 && a.ubg0) gbu = 0.0f;
 
         if (ULONG && run_long) {
             // a segment of a long run: its part of the user gradient, for k_user_stitch
@@ -628,6 +632,84 @@ __global__ __launch_bounds__(256) void k_score_pass(slk_pass_args a) {
 }
 
 // (k_adaptive_select: slk_kernels.h -- the row-sharded path launches it too)
+
+// ---------------------------------------------------------------------------------------
+// sampled softmax (include/spotlight_hip.h: SLK_LOSS_SOFTMAX) behind k_score_pass: per interaction the softmax over its
+// positive and its OWN n draws -- pairs 0 .. n of sk[(k0 + k) * NP + .], contiguous -- the loss term and dL/dscore of every
+// pair.  A group of G lanes per interaction (G: slk_softmax_group(NP), a function of n alone), lane t taking pairs t, t + G,
+// ...: the lanes of a group read consecutive floats, the groups of a wavefront consecutive interactions.  NP <= 64 is one pair
+// per lane, kept in a register; above, the wavefront strides and re-reads its pairs from the cache (the scores of one
+// interaction are at most 4 KB).  The order of the max and of the sums is the one the header states: per lane in pair order,
+// then the xor butterfly G/2 .. 1 -- grid, bm and chunking do not enter, and there is no other form of this kernel.
+// Every entry of this minibatch's gk is written (no memset before the launch); w / wsum as in k_adaptive_select.
+// ---------------------------------------------------------------------------------------
+static inline int slk_softmax_group(int NP) {
+    int g = 2;
+    while (g < NP && g < 64) g <<= 1;
+    return g;
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void k_softmax_loss(const float *sk, float *gk, uint32_t k0, uint32_t bm, int nn, float inv_b,
+                                                      double *loss_partial, const float *w, const double *wsum) {
+    __shared__ double red[256];
+    constexpr uint32_t GPB = 256 / G;
+    const int NP = nn + 1;
+    const int lane = (int)(threadIdx.x % G);
+    const uint32_t grp = threadIdx.x / G;
+    const float inv_W = w ? 1.0f / (float)*wsum : 0.0f;
+    double lsum = 0.0;
+    // (every group of a workgroup makes the same number of trips: the shuffles inside are taken by whole wavefronts)
+    for (uint32_t base = blockIdx.x * GPB; base < bm; base += gridDim.x * GPB) {
+        const uint32_t k = base + grp;
+        const bool on = k < bm;
+        const size_t at0 = (size_t)(k0 + (on ? k : 0u)) * NP;
+        const float s_own = (on && lane < NP) ? sk[at0 + lane] : 0.0f;  // this lane's first pair
+        float m = -INFINITY;
+        if (on)
+            for (int j = lane; j < NP; j += G) m = fmaxf(m, j == lane ? s_own : sk[at0 + j]);
+#pragma unroll
+        for (int x = G / 2; x >= 1; x >>= 1) m = fmaxf(m, __shfl_xor(m, x, G));
+        float zn = 0.0f, e_own = 0.0f;
+        if (on)
+            for (int j = lane; j < NP; j += G) {
+                const float e = expf((j == lane ? s_own : sk[at0 + j]) - m);
+                if (j == lane) e_own = e;
+                if (j > 0) zn += e;
+            }
+#pragma unroll
+        for (int x = G / 2; x >= 1; x >>= 1) zn += __shfl_xor(zn, x, G);
+        const float e0 = __shfl(e_own, 0, G), s0 = __shfl(s_own, 0, G);
+        if (!on) continue;
+        const float Z = e0 + zn;
+        const float wc = w ? w[k0 + k] : 1.0f;
+        for (int j = lane; j < NP; j += G) {
+            const float e = j == lane ? e_own : expf(sk[at0 + j] - m);
+            const float unit = j == 0 ? zn / Z : e / Z;
+            const float g = w ? slk_weight_scale(unit, wc, inv_W) : unit * inv_b;
+            gk[at0 + j] = j == 0 ? -g : g;
+        }
+        if (lane == 0) {
+            const float l = logf(Z) - (s0 - m);
+            lsum += w ? (double)wc * (double)l : (double)l;
+        }
+    }
+    const double tot = slk_block_sum_256(lsum, red);
+    // (weighted: the partials leave already divided by the weight sum -- the item pass's finalisation then runs with inv_b = 1)
+    if (threadIdx.x == 0) loss_partial[blockIdx.x] = w ? tot * (double)inv_W : tot;
+}
+
+typedef void (*slk_softmax_fn)(const float *, float *, uint32_t, uint32_t, int, float, double *, const float *, const double *);
+static slk_softmax_fn softmax_loss_fn(int g) {
+    switch (g) {
+        case 2: return k_softmax_loss<2>;
+        case 4: return k_softmax_loss<4>;
+        case 8: return k_softmax_loss<8>;
+        case 16: return k_softmax_loss<16>;
+        case 32: return k_softmax_loss<32>;
+        default: return k_softmax_loss<64>;
+    }
+}
 
 // ---------------------------------------------------------------------------------------
 // explicit feedback (spotlight/factorization/explicit.py:223-234, losses.py:169-244): per interaction
@@ -1149,7 +1231,7 @@ struct train_plan {  // everything derived from a call and the ctx's options bef
     // expl: explicit feedback (ratings, no negatives); fused: ... whose user pass forms score, loss and dL/dscore itself (option
     // "explicit_fused"); pre: dL/dscore is computed before the user pass; weighted: interaction weights -- every loss staged
     // (`pre`, never `fused`, never the persistent route), the pair losses with their NP = 2 through k_pair_loss_weighted
-    bool bloom, adaptive, expl, fused, pre, dense, late, weighted;
+    bool bloom, adaptive, multi, expl, fused, pre, dense, late, weighted;
     int nn, NP, umode, nsets;
     int64_t bsz, mb_per_chunk, chunk_cap, occ_mult;
     // chunk ck is [ck * chunk_cap, min(n, (ck + 1) * chunk_cap)): nc_max interactions in the largest (= the first); 0 chunks: an empty call
@@ -1232,7 +1314,7 @@ SLK_EXPORT int slk_bilinear_train_explicit(slk_ctx *ctx, const slk_tables *table
                                            void *stream) {
     if (ctx && !slk_loss_is_explicit(loss))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: loss kind %d%s is not regression/poisson/logistic", loss,
-                        loss == SLK_LOSS_WARP ? " (warp)" : "");
+                        loss == SLK_LOSS_WARP ? " (warp)" : (loss == SLK_LOSS_SOFTMAX ? " (softmax)" : ""));
     if (ctx && n > 0 && !d_ratings) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train_explicit: d_ratings is NULL");
     return run_training(ctx, {train_call::TRAIN, tables, optim, d_users, d_items, d_ratings, nullptr, nullptr, d_mb_loss, n,
                               batch_size, loss, 0, (hipStream_t)stream});
@@ -1266,18 +1348,21 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
     if ((rc = slk_check_optim(ctx, optim, 15u))) return rc;
     if (n < 0 || c.batch_size < 1) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_train: n %lld batch_size %lld",
                                                    (long long)n, (long long)c.batch_size);
-    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_WARP)
+    if (c.loss < SLK_LOSS_POINTWISE || c.loss > SLK_LOSS_SOFTMAX)
         return slk_fail(ctx, SLK_EINVAL, "unknown loss kind %d", c.loss);
-    // (`adaptive`: a COLUMN loss -- adaptive hinge or warp; they differ in k_adaptive_select's rule alone)
+    // (`adaptive`: a COLUMN loss -- adaptive hinge or warp; they differ in k_adaptive_select's rule alone.  `multi`: n_neg draws
+    // per positive, all scored ahead of the user pass -- the column losses and sampled softmax, whose 1 + n occurrences are ALL
+    // live: never `late`, never the persistent route)
     p.adaptive = slk_loss_is_column(c.loss);
+    p.multi = slk_loss_is_multi(c.loss);
     p.expl = slk_loss_is_explicit(c.loss);
     if (p.expl != (c.ratings != nullptr) && !reserve)
         return slk_fail(ctx, SLK_EINVAL, "ratings go with (and only with) the regression/poisson/logistic losses");
     p.weighted = c.weights != nullptr;
     p.fused = p.expl && ctx->opt_explicit_fused && !p.weighted;
-    p.pre = p.adaptive || p.expl || p.weighted;
+    p.pre = p.multi || p.expl || p.weighted;
     p.umode = p.fused ? 2 : (p.pre ? 1 : 0);
-    p.nn = p.adaptive ? c.n_neg : (p.expl ? 0 : 1);
+    p.nn = p.multi ? c.n_neg : (p.expl ? 0 : 1);
     if (!p.expl && (p.nn < 1 || p.nn > 1024)) return slk_fail(ctx, SLK_EINVAL, "num_negative_samples %d outside [1, 1024]", p.nn);
     p.NP = p.nn + 1;
     p.dense = slk_opt_is_dense(optim->kind);
@@ -1316,7 +1401,8 @@ static int plan_training(slk_ctx *ctx, const train_call &c, train_plan *plan) {
         return slk_fail(ctx, SLK_EINVAL, "batch_size * lookups per interaction must be < 2^31");
     // the persistent route (slk_epoch.hip) keeps per-(minibatch, workgroup) loss partials and counts barriers in 32 bits:
     // at most 2^13 minibatches per launch (16 MB of partials at 256 workgroups)
-    const bool maybe_epoch = ctx->opt_epoch_kernel && !ctx->epoch_refused && bsz <= ctx->opt_epoch_max_batch && !p.weighted;
+    const bool maybe_epoch = ctx->opt_epoch_kernel && !ctx->epoch_refused && bsz <= ctx->opt_epoch_max_batch && !p.weighted &&
+                            c.loss != SLK_LOSS_SOFTMAX;
     if (maybe_epoch && mb_per_chunk > ((int64_t)1 << 13)) mb_per_chunk = (int64_t)1 << 13;
     p.mb_per_chunk = mb_per_chunk;
     // chunks of chunk_cap.  Chunking is value-neutral: the negatives of a call are one contiguous draw however
@@ -1516,6 +1602,9 @@ static void pick_kernels(slk_ctx *ctx, const train_plan &p, const slk_optim *opt
     train_kernels &k = *kernels;
     const int upd = slk_upd_for(optim->kind), umode = p.umode;
     const bool bloom = p.bloom;
+    // sampled softmax over a plain item table: every occurrence of the item pass is live (a bloom item table keeps the
+    // SLK_ITEM_SNAP forms of its bias and row passes)
+    const bool all_live = p.multi && !p.adaptive;
     k = train_kernels{};
 #define SLK_PICK(V_, G_)                                                                    \
     do {                                                                                    \
@@ -1525,6 +1614,7 @@ static void pick_kernels(slk_ctx *ctx, const train_plan &p, const slk_optim *opt
         if (!bloom) k.upass_long = user_pass_long_fn<V_, G_>(upd, umode);                   \
         if (!bloom) k.ustitch = user_stitch_fn<V_, G_>(upd);                                \
         k.ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAP>(upd);                             \
+        if (all_live) k.ipass = slk_item_pass_fn<V_, G_, SLK_ITEM_SNAPALL>(upd);            \
         k.spass = k_score_pass<V_, G_>;                                                     \
         if (p.pingpong) {                                                                   \
             k.upass = user_pass_pp_fn<V_, G_, false, false>(upd);                           \
@@ -1718,6 +1808,7 @@ static void chunk_pass_args(slk_ctx *ctx, const train_plan &p, const train_call 
     // zero gradient is an exact no-op: nothing of the table is read or written by the pair-mode user pass
     a.ubz = (tables->flags & SLK_TABLES_USER_BIAS_ZERO) && (c.loss == SLK_LOSS_BPR || c.loss == SLK_LOSS_HINGE) && !p.bloom &&
             slk_opt_zero_is_noop(optim->kind) && ctx->opt_user_bias_zero_hint;
+    a.ubg0 = c.loss == SLK_LOSS_SOFTMAX;
     a.nt = ctx->opt_nt;
     if (p.fused) a.ratings = c.ratings + chunk_begin(p, ck);  // the user pass forms score, loss and dL/dscore itself (one pair per interaction)
 }
@@ -1742,7 +1833,7 @@ static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, c
     slk_prof_begin(ctx, SLK_K_SCORE, s);
     hipLaunchKernelGGL(k.spass, dim3(mb.ugrid), dim3(256), 0, s, a);
     SLK_LAUNCH_CHECK(ctx, "k_score_pass");
-    const unsigned sgrid = slk_grid_for(ctx, mb.bm, 256);
+    unsigned sgrid = slk_grid_for(ctx, mb.bm, 256);
     // interaction weights: chunk-local as the ratings are; this minibatch's W in the chunk's sums (weight_sums)
     const float *const wts = p.weighted ? c.weights + chunk_begin(p, ck) : nullptr;
     const double *const wsum = p.weighted ? (const double *)ctx->extra[BL_WSUM].p + mb.b0 / (uint32_t)p.bsz : nullptr;
@@ -1751,7 +1842,7 @@ static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, c
                            c.ratings + chunk_begin(p, ck), wts, f32p(ctx->gk), mb.b0, mb.bm, (int)c.loss, wsum,
                            (double *)ctx->losspart.p);
         SLK_LAUNCH_CHECK(ctx, "k_explicit_loss_weighted");
-    } else if (p.weighted && !p.adaptive) {
+    } else if (p.weighted && !p.multi) {
         hipLaunchKernelGGL(k_pair_loss_weighted, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, wts, f32p(ctx->gk), mb.b0,
                            mb.bm, (int)c.loss, wsum, (double *)ctx->losspart.p);
         SLK_LAUNCH_CHECK(ctx, "k_pair_loss_weighted");
@@ -1759,6 +1850,12 @@ static int score_stage(slk_ctx *ctx, const train_plan &p, const train_call &c, c
         hipLaunchKernelGGL(k_explicit_loss, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, c.ratings + chunk_begin(p, ck),
                            f32p(ctx->gk), mb.b0, mb.bm, (int)c.loss, a.inv_b, (double *)ctx->losspart.p);
         SLK_LAUNCH_CHECK(ctx, "k_explicit_loss");
+    } else if (!p.adaptive) {  // sampled softmax: a lane group per interaction
+        const int sg = slk_softmax_group(p.NP);
+        sgrid = slk_grid_for(ctx, mb.bm, 256u / (unsigned)sg);
+        hipLaunchKernelGGL(softmax_loss_fn(sg), dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, f32p(ctx->gk), mb.b0, mb.bm,
+                           p.nn, a.inv_b, (double *)ctx->losspart.p, wts, wsum);
+        SLK_LAUNCH_CHECK(ctx, "k_softmax_loss");
     } else {
         hipLaunchKernelGGL(k_adaptive_select<0>, dim3(sgrid), dim3(256), 0, s, (const float *)ctx->sk.p, f32p(ctx->gk), mb.b0, mb.bm,
                            p.nn, a.inv_b, (double *)ctx->losspart.p, p.late ? (const uint32_t *)pb.ipay[0].p : (const uint32_t *)nullptr,

@@ -18,6 +18,10 @@
 static inline bool slk_loss_is_explicit(int loss) { return loss >= SLK_LOSS_REGRESSION && loss <= SLK_LOSS_LOGISTIC; }
 static inline bool slk_loss_is_column(int loss) { return loss == SLK_LOSS_ADAPTIVE_HINGE || loss == SLK_LOSS_WARP; }
 static inline const char *slk_column_loss_name(int loss) { return loss == SLK_LOSS_WARP ? "warp" : "adaptive hinge"; }
+// The MULTI-NEGATIVE losses -- n_neg draws per positive, 1 + n_neg lookups per interaction, dL/dscore formed ahead of the user
+// pass: the column losses and sampled softmax.  Softmax is NOT a column loss: each positive meets its own user's draws and every
+// one of the 1 + n_neg occurrences is live (no late live list, no persistent kernel).
+static inline bool slk_loss_is_multi(int loss) { return slk_loss_is_column(loss) || loss == SLK_LOSS_SOFTMAX; }
 
 // Occupancy target of a kernel in waves per SIMD (caps its VGPR budget at 512 / n).  hipcc only;
 // the test harness's host build of these sources ignores it.

@@ -732,6 +732,8 @@ static int epoch_mode_of(int loss) {
 bool slk_epoch_eligible(const slk_ctx *ctx, const slk_tables *tables, const slk_optim *optim, int64_t bsz, int loss,
                         bool bloom) {
     if (!ctx->opt_epoch_kernel || ctx->epoch_refused || bloom) return false;
+    // sampled softmax: 1 + n live pairs per interaction; the persistent kernel records two -- the launch path at every size
+    if (loss == SLK_LOSS_SOFTMAX) return false;
     // one-negative pair losses, the explicit-feedback losses, adaptive hinge over ALL 1 + n occurrences (the chunk-sorted item
     // list; the launch path's per-minibatch live lists start at adaptive_late_min_batch, far above epoch_max_batch)
     if (slk_loss_is_column(loss) &&

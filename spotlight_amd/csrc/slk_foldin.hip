@@ -351,6 +351,8 @@ SLK_EXPORT int slk_bilinear_foldin(slk_ctx *ctx, const slk_tables *tables, slk_o
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: n_steps %lld and n_new_users %lld must be at least 1", (long long)n_steps,
                         (long long)n_new_users);
     if (n < 0) return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: n %lld is negative", (long long)n);
+    if (loss == SLK_LOSS_SOFTMAX)  // (every candidate live: not this gather's pair / column rule; the host takes its generic route)
+        return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: softmax (loss kind %d) is not built for fold-in", loss);
     if (loss < SLK_LOSS_POINTWISE || loss > SLK_LOSS_WARP || slk_loss_is_explicit(loss))
         return slk_fail(ctx, SLK_EINVAL, "slk_bilinear_foldin: loss %d is not an implicit-feedback loss (explicit feedback needs ratings)",
                         loss);

@@ -150,6 +150,8 @@ struct slk_pass_args {
     slk_opt_hyper hyper;
     int nt;                // cache-policy bits (ctx option "nt")
     int ubz;               // 1: the user biases are identically zero and this pass cannot change them (slk_tables::flags): not fetched
+    int ubg0;              // 1: the user-bias gradient of this loss is exactly zero by construction (sampled softmax): the staged
+                           // user pass (UMODE 1) applies 0.0f, not the fp32 residue of the cancelling sum
     // user-row ping-pong of a training scope (slk_user_pingpong_begin, pair mode over a plain user table): the user table
     // exists twice.  uflag[u] = the copy that holds user u's current row (0 = P[0], 1 = P0alt).  The user pass reads the row
     // from that copy, writes the UPDATED row to the other one and flips the flag; the copy it read still holds the pre-step
@@ -183,9 +185,11 @@ constexpr int slk_upd_kind(int upd) {
 //   SNAPPP  as SNAP with NP == 2 inside a user-row ping-pong scope: no record; gsn[r - begin*2] = {g_s, src} (8 bytes),
 //         u_old = the row of user (src & 0x7fffffff) in the copy (src >> 31) of the user table (slk_pass_args::P0alt)
 //   SNAPPPS as SNAPPP; occurrences whose item occurs once in the minibatch (msorted[e] == 0) are skipped: the user pass updated them
-enum slk_item_mode { SLK_ITEM_SNAP = 0, SLK_ITEM_SEQ = 1, SLK_ITEM_ROW = 2, SLK_ITEM_BLK = 3, SLK_ITEM_SNAPPP = 4, SLK_ITEM_SNAPPPS = 5 };
+// (SLK_ITEM_SNAPALL: SLK_ITEM_SNAP for a call whose every occurrence carries a gradient -- sampled softmax: slk_item_contrib)
+enum slk_item_mode { SLK_ITEM_SNAP = 0, SLK_ITEM_SEQ = 1, SLK_ITEM_ROW = 2, SLK_ITEM_BLK = 3, SLK_ITEM_SNAPPP = 4, SLK_ITEM_SNAPPPS = 5,
+                     SLK_ITEM_SNAPALL = 6 };
 #define SLK_ITEM_IS_PP(MODE) ((MODE) == SLK_ITEM_SNAPPP || (MODE) == SLK_ITEM_SNAPPPS)
-#define SLK_ITEM_IS_SNAP(MODE) ((MODE) == SLK_ITEM_SNAP || SLK_ITEM_IS_PP(MODE))
+#define SLK_ITEM_IS_SNAP(MODE) ((MODE) == SLK_ITEM_SNAP || (MODE) == SLK_ITEM_SNAPALL || SLK_ITEM_IS_PP(MODE))
 
 // Exchange buffers of the row-sharded path (slk_shard.hip): slots come in blocks of 64, a block is 64 rows of D floats
 // followed by the 64 scalars (bias / bias gradient) of those rows.  Every row of a D = 64 table is then one aligned
@@ -344,12 +348,16 @@ __device__ __forceinline__ void slk_item_contrib(const slk_pass_args &a, uint32_
             const slk_vec<VEC> u = on ? slk_vload_if_nt<VEC>(urow + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
 #pragma unroll
             for (int i = 0; i < VEC; ++i) c.v[i] = gb * u.v[i];
-        } else if (MODE == SLK_ITEM_SNAP) {
+        } else if (MODE == SLK_ITEM_SNAP || MODE == SLK_ITEM_SNAPALL) {
             gb = a.gsn[r - a.begin * NP];
             // several negatives per interaction (adaptive hinge): only the positive and the selected
             // negative carry a gradient, so the row is fetched only when dL/dscore != 0 (a dependent
-            // load; with one negative every occurrence is live and both loads are issued at once)
-            const slk_vec<VEC> u = (on && (NP <= 2 || gb != 0.0f)) ? slk_vload_if_nt<VEC>(rec + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
+            // load; with one negative every occurrence is live and both loads are issued at once).
+            // SLK_ITEM_SNAPALL (sampled softmax): every occurrence is live, so the row is fetched without looking at dL/dscore
+            // and the tile's gathers are all in flight together (a compile-time form: as a run-time flag in this condition the
+            // loads stayed behind the branch and gained nothing, DESIGN.md 4b "Sampled softmax").  An occurrence whose dL/dscore
+            // underflowed to exactly 0 then adds 0 * u where the skipped load adds a zero vector: the same for every finite row.
+            const slk_vec<VEC> u = (on && (MODE == SLK_ITEM_SNAPALL || NP <= 2 || gb != 0.0f)) ? slk_vload_if_nt<VEC>(rec + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
 #pragma unroll
             for (int i = 0; i < VEC; ++i) c.v[i] = gb * u.v[i];
         } else {

@@ -712,6 +712,8 @@ SLK_EXPORT int slk_shard_user_pass(slk_ctx *ctx, const slk_tables *local, const 
     if (!ctx) return SLK_EINVAL;
     if (loss == SLK_LOSS_WARP)  // (answered first: whatever else the call holds, this path has no warp selection)
         return slk_fail(ctx, SLK_EINVAL, "slk_shard_user_pass: warp (loss kind %d) is not built on the row-sharded path", loss);
+    if (loss == SLK_LOSS_SOFTMAX)
+        return slk_fail(ctx, SLK_EINVAL, "slk_shard_user_pass: softmax (loss kind %d) is not built on the row-sharded path", loss);
     int vec, g, rc;
     if ((rc = slk_check_tables(ctx, local, 15u, &vec, &g, /*shadow_ok=*/true))) return rc;
     if ((rc = check_plain(ctx, local))) return rc;

@@ -40,6 +40,10 @@ _USER_PINGPONG_MIN_BATCH = 1 << 17
 # The column losses: num_negative_samples draws per positive, viewed as [n, B] (implicit.py:266-275), one selection per column --
 # adaptive hinge the largest candidate, warp the first violating one (include/spotlight_hip.h: SLK_LOSS_WARP)
 COLUMN_LOSSES = ('adaptive_hinge', 'warp')
+# The multi-negative losses: num_negative_samples draws per positive, ONE draw of B * n per minibatch.  The column losses view it
+# as [n, B]; sampled softmax keeps flat draw f with the user it was drawn for -- negative f % n of positive f // n
+# (include/spotlight_hip.h: SLK_LOSS_SOFTMAX)
+MULTI_NEGATIVE_LOSSES = COLUMN_LOSSES + ('softmax',)
 
 
 def _engine_for(device):
@@ -269,7 +273,7 @@ class _ImplicitEpochs(object):
         self.call = (n, model._batch_size, model._loss, model._num_negative_samples)
         self.mb_loss = torch.empty((n + model._batch_size - 1) // model._batch_size, dtype=torch.float32, device=device)
         self.slots, self.scopes, self.sources, self.weighted, self.side = [], [], None, False, None
-        self.seen = self.d_cand = self.d_counts = None  # verified negatives (verify_with)
+        self.seen = self.d_cand = self.d_counts = self.d_rep = None  # verified negatives (verify_with)
         self.tries, self.nn = 1, 1
 
     def verify_with(self, seen, tries, nn):
@@ -279,6 +283,9 @@ class _ImplicitEpochs(object):
         summed on the device over the whole fit()."""
         self.seen, self.tries, self.nn = seen, int(tries), int(nn)
         bsz = self.call[1]
+        # sampled softmax: flat slot f of a minibatch belongs to user f // nn, not to the column f % bm of the view(nn, bm) that
+        # slk_verify_negatives checks against -- the same flat layout read as ONE negative row over the users repeated user-major
+        self.own_user = self.call[2] == 'softmax' and self.nn > 1
         per_mb = bsz * self.nn * self.tries
         self.group = max(1, _VERIFY_MAX_CANDIDATES // per_mb) * bsz  # interactions per draw: whole minibatches
         self.d_cand = torch.empty(min(self.n, self.group) * self.nn * self.tries, dtype=torch.int64, device=self.device)
@@ -291,7 +298,19 @@ class _ImplicitEpochs(object):
         for lo in range(0, self.n, self.group):
             m = min(self.group, self.n - lo)
             _sampling.draw_items(engine, self.num_items, m * self.nn * self.tries, self.d_cand.data_ptr(), stream, self.dist)
-            engine.verify_negatives(d_users.data_ptr() + 8 * lo, m, self.call[1], self.nn, self.tries, self.d_cand.data_ptr(),
+            users, m_v, bsz_v, nn_v = d_users.data_ptr() + 8 * lo, m, self.call[1], self.nn
+            if self.own_user:
+                if self.d_rep is None:
+                    self.d_rep = torch.empty(min(self.n, self.group) * self.nn, dtype=torch.int64, device=self.device)
+                # the copy goes to the very stream the draw and the selection are enqueued on, whichever stream is current in
+                # this thread (a handle of 0 is the device's null stream: torch's default stream)
+                side = None
+                if self.device.type == 'cuda':
+                    side = torch.cuda.ExternalStream(stream, device=self.device) if stream else torch.cuda.default_stream(self.device)
+                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                    self.d_rep[:m * self.nn].view(m, self.nn).copy_(d_users[lo:lo + m].unsqueeze(1).expand(m, self.nn))
+                users, m_v, bsz_v, nn_v = self.d_rep.data_ptr(), m * self.nn, self.call[1] * self.nn, 1
+            engine.verify_negatives(users, m_v, bsz_v, nn_v, self.tries, self.d_cand.data_ptr(),
                                     seen.d_off.data_ptr(), seen.d_items.data_ptr(), seen.num_users,
                                     d_neg.data_ptr() + 8 * lo * self.nn, self.d_counts.data_ptr(), stream=stream)
 
@@ -373,6 +392,14 @@ class ImplicitFactorizationModel(object):
       a positive without a violator contributes nothing.  The RandomState is consumed exactly as by `loss='adaptive_hinge'` with
       the same `num_negative_samples`.  The rank estimate assumes uniform draws: under `negative_sampling='popularity'` it is a
       popularity-weighted rank (include/spotlight_hip.h: SLK_LOSS_WARP; `spotlight_amd.losses.warp_loss` on the autograd route).
+    * `loss='softmax'` (not in the reference): sampled softmax (InfoNCE).  A positive and ITS OWN `num_negative_samples` draws go
+      into one softmax, `logsumexp([pos; negs]) - pos`, and every candidate carries a gradient in proportion to how wrongly it is
+      ranked -- no margin, no rank estimate.  The draws are adaptive hinge's (one draw of B * n per minibatch; the RandomState is
+      consumed exactly as by `loss='adaptive_hinge'` with the same `num_negative_samples`), but each draw stays with the user it
+      was drawn for instead of the reference's `view(n, B)` column.  Composes with `use_weights`, `negative_sampling` (no logQ
+      correction: popular items are then over-penalised in proportion to their sampling rate) and `verify_negatives` (each draw is
+      checked against its own user); fold_in() takes its generic route (include/spotlight_hip.h: SLK_LOSS_SOFTMAX;
+      `spotlight_amd.losses.softmax_loss` on the autograd route).
     * `negative_sampling` (not in the reference): what the negatives are drawn from.  'uniform' or None: every item alike
       (`RandomState.randint`, the reference's sampler).  'popularity': in proportion to
       `count(item) ** negative_sampling_power` (word2vec's unigram distribution; default power 0.75), the counts taken over
@@ -409,7 +436,7 @@ class ImplicitFactorizationModel(object):
                  sparse=False, random_state=None, num_negative_samples=5, negative_sampling='uniform',
                  negative_sampling_power=0.75, use_weights=False, verify_negatives=False, verify_tries=4):
 
-        assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge', 'warp')
+        assert loss in ('pointwise', 'bpr', 'hinge', 'adaptive_hinge', 'warp', 'softmax')
         _sampling.check_negative_sampling(negative_sampling)
         self._verify_tries = _sampling.check_verify_tries(verify_tries)
         self._verify_negatives = bool(verify_negatives)
@@ -537,7 +564,7 @@ class ImplicitFactorizationModel(object):
             self._initialize(interactions)
 
         n = len(user_ids)
-        nn = self._num_negative_samples if self._loss in COLUMN_LOSSES else 1
+        nn = self._num_negative_samples if self._loss in MULTI_NEGATIVE_LOSSES else 1
         autograd = getattr(self, '_autograd_route', False)
         # non-uniform negatives are handed in at every size (the two-lane schedule): the three-stage pipeline's
         # slk_bilinear_prefetch draws uniform ones ahead of time
@@ -626,7 +653,8 @@ class ImplicitFactorizationModel(object):
         from spotlight_amd.torch_utils import minibatch, shuffle
         loss_func = {'pointwise': _losses.pointwise_loss, 'bpr': _losses.bpr_loss, 'hinge': _losses.hinge_loss,
                      'adaptive_hinge': _losses.adaptive_hinge_loss,
-                     'warp': lambda pos, neg, **kw: _losses.warp_loss(pos, neg, self._num_items, **kw)}[self._loss]
+                     'warp': lambda pos, neg, **kw: _losses.warp_loss(pos, neg, self._num_items, **kw),
+                     'softmax': _losses.softmax_loss}[self._loss]
         device = next(self._net.parameters()).device
         self._net.train(True)
 
@@ -640,8 +668,10 @@ class ImplicitFactorizationModel(object):
             # ONE draw of verify_tries * n_draws candidates, viewed [tries][n_draws / B][B]
             cand = sample_items(self._num_items, self._verify_tries * n_draws, random_state=self._random_state,
                                 p=self._item_distribution)
-            picked, replaced, unresolved = _sampling.verify_negatives(cand, batch_user.cpu().numpy(), seen,
-                                                                      n_draws // len(batch_user), self._verify_tries)
+            users, per_user = batch_user.cpu().numpy(), n_draws // len(batch_user)
+            if self._loss == 'softmax':  # slot f belongs to user f // n: one "negative row" over the users repeated user-major
+                users, per_user = np.repeat(users, per_user), 1
+            picked, replaced, unresolved = _sampling.verify_negatives(cand, users, seen, per_user, self._verify_tries)
             for k, v in enumerate((n_draws, replaced, unresolved)):
                 counts[k] += v
             return torch.from_numpy(np.ascontiguousarray(picked.reshape(-1))).to(device)
@@ -662,6 +692,13 @@ class ImplicitFactorizationModel(object):
                     negative_items = negatives_for(batch_user, batch_size * n).view(batch_size * n)
                     batch_user_rep = batch_user.view(batch_size, 1).expand(batch_size, n).reshape(-1)
                     negative_prediction = self._net(batch_user_rep, negative_items).view(n, batch_size)
+                elif self._loss == 'softmax':
+                    # the same draw of B * n and the same user-major repeat, but each positive meets ITS OWN draws: [B, n] -> [n, B]
+                    n = self._num_negative_samples
+                    batch_size = batch_user.size(0)
+                    negative_items = negatives_for(batch_user, batch_size * n).view(batch_size * n)
+                    batch_user_rep = batch_user.view(batch_size, 1).expand(batch_size, n).reshape(-1)
+                    negative_prediction = self._net(batch_user_rep, negative_items).view(batch_size, n).t()
                 else:
                     negative_prediction = self._net(batch_user, negatives_for(batch_user, len(batch_user)))
                 self._optimizer.zero_grad()

@@ -334,7 +334,7 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
 
     All four losses (adaptive hinge: a score phase and a selection over the whole minibatch in front of the user pass,
     ShardedBilinearTrainer.run_chunk); loss='warp' is not built here and raises NotImplementedError at construction, before
-    anything is drawn.  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
+    anything is drawn, and so does loss='softmax'.  Restriction of the exchange path: plain (non-bloom) tables.  Interaction weights are not
     sharded yet: use_weights=True raises ValueError at construction.  Verified negatives are not built here either:
     verify_negatives=True raises NotImplementedError at construction, before anything is drawn.
 
@@ -348,6 +348,8 @@ class ShardedImplicitFactorizationModel(ImplicitFactorizationModel):
         # (before the base constructor: it draws the model's seed from random_state)
         if kwargs.get('loss', args[0] if args else 'pointwise') == 'warp':
             raise NotImplementedError("loss='warp': warp is not built on the row-sharded path")
+        if kwargs.get('loss', args[0] if args else 'pointwise') == 'softmax':
+            raise NotImplementedError("loss='softmax': sampled softmax is not built on the row-sharded path")
         if kwargs.get('verify_negatives', args[15] if len(args) > 15 else False):
             raise NotImplementedError('verify_negatives=True: verified negatives are not built on the row-sharded path')
         super(ShardedImplicitFactorizationModel, self).__init__(*args, **kwargs)

@@ -118,7 +118,8 @@ def generic_steps(model, table, bias, off, items, neg, emb, b, T):
     from spotlight_amd import losses as _losses
     loss_func = {'pointwise': _losses.pointwise_loss, 'bpr': _losses.bpr_loss, 'hinge': _losses.hinge_loss,
                  'adaptive_hinge': _losses.adaptive_hinge_loss,
-                 'warp': lambda pos, neg: _losses.warp_loss(pos, neg, model._num_items)}[model._loss]
+                 'warp': lambda pos, neg: _losses.warp_loss(pos, neg, model._num_items),
+                 'softmax': _losses.softmax_loss}[model._loss]
     device = table.device
     lens = np.diff(off)
     live = np.nonzero(lens > 0)[0]
@@ -130,7 +131,7 @@ def generic_steps(model, table, bias, off, items, neg, emb, b, T):
     row_of = torch.from_numpy(np.repeat(np.arange(live.size), lens[live])).to(device)
     d_items = torch.from_numpy(items).to(device)
     bounds = np.concatenate([[0], np.cumsum(lens[live])])
-    adaptive = model._loss in _host.COLUMN_LOSSES  # every candidate row of the column goes to the loss
+    adaptive = model._loss in _host.MULTI_NEGATIVE_LOSSES  # every candidate row of the column goes to the loss
     score =lambda ids: (u[row_of] * table[ids]).sum(1) + ub[row_of] + bias[ids]
     for t in range(T):
         opt.zero_grad()
@@ -160,7 +161,7 @@ def fold_in(model, interactions, n_iter=None, init=None, negatives=None, generic
     if T < 1:
         raise ValueError('n_iter must be at least 1, got {!r}'.format(n_iter))
     dim = int(table.shape[1])
-    nn = model._num_negative_samples if model._loss in _host.COLUMN_LOSSES else 1
+    nn = model._num_negative_samples if model._loss in _host.MULTI_NEGATIVE_LOSSES else 1
     if H < 1:
         return np.zeros((0, dim), np.float32), np.zeros(0, np.float32)
     device = table.device
@@ -168,7 +169,9 @@ def fold_in(model, interactions, n_iter=None, init=None, negatives=None, generic
     _refuse_inside_open_scope(engine, stream, table, bias, model._num_items)
     emb, b = _initial_rows(model, init, H, dim)
     neg = _negatives(model, negatives, T, nn, n, device, engine, stream)
-    if plain and not generic:
+    # (sampled softmax: every candidate of a position is live -- not the fused gather's pair / column rule; slk_bilinear_foldin
+    # refuses it and the generic route, whose [nn, n] negatives are per position already, trains through losses.softmax_loss)
+    if plain and not generic and model._loss != 'softmax':
         u, ub = torch.from_numpy(emb).to(device), torch.from_numpy(b).to(device)
         try:
             binding = _host._OptimizerBinding(_fresh_optimizer(model, [u, ub]), [u, ub], model._sparse)

@@ -75,6 +75,19 @@ def warp_loss(positive_predictions, negative_predictions, num_items, mask=None, 
     return _masked_mean(terms, mask, weights)
 
 
+def softmax_loss(positive_predictions, negative_predictions, mask=None, weights=None):
+    """Sampled softmax (InfoNCE; not in the reference): -log of the positive's share of the softmax over the positive and its
+    OWN sampled negatives.  negative_predictions is [n, B]: column c holds the n negatives drawn FOR positive c (the same
+    user) -- not the reference's view(n, B) of a user-major draw, whose column c holds other users' draws.  Per column
+
+        l = logsumexp([pos; neg_1 .. neg_n]) - pos
+
+    Every candidate carries a gradient, softmax(.)_j, the positive softmax(.)_0 - 1.  A negative equal to the positive is not
+    masked; no logQ correction under negative_sampling='popularity'   (include/spotlight_hip.h: SLK_LOSS_SOFTMAX)."""
+    scores = torch.cat([positive_predictions.unsqueeze(0), negative_predictions], 0)
+    return _masked_mean(torch.logsumexp(scores, 0) - positive_predictions, mask, weights)
+
+
 def regression_loss(observed_ratings, predicted_ratings, weights=None):
     """Mean squared error   (losses.py:169-191)."""
     assert_no_grad(observed_ratings)
