@@ -24,40 +24,46 @@ def _hooks():
 class _Lookup(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, weight, ids, bloom, padding_idx, sparse):
+    def forward(ctx, weight, ids, bloom, padding_idx, sparse, device):
+        """`device`: where the kernels run.  A table that lives elsewhere (in host memory) is staged onto it here and the result
+        handed back on the table's own device -- inside the Function, not through autograd's copy nodes: the node of
+        `weight.to(device)` cannot carry a sparse gradient home (it converts to the table's options, layout included)."""
         host = _hooks()
         if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() != 2:
             raise RuntimeError('embedding tables must be contiguous 2-D fp32 tensors')
-        engine = host._engine_for(weight.device)
-        stream = host._stream_for(weight.device)
-        flat = ids.reshape(-1).to(device=weight.device, dtype=torch.int64).contiguous()
-        rows, dim = weight.shape
-        out = torch.empty((flat.numel(), dim), dtype=torch.float32, device=weight.device)
-        engine.embedding_forward(weight.data_ptr(), rows, dim, bloom, flat.data_ptr(), flat.numel(), out.data_ptr(),
+        home = weight.device
+        table = weight if home == device else weight.to(device)
+        engine = host._engine_for(device)
+        stream = host._stream_for(device)
+        flat = ids.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+        rows, dim = table.shape
+        out = torch.empty((flat.numel(), dim), dtype=torch.float32, device=device)
+        engine.embedding_forward(table.data_ptr(), rows, dim, bloom, flat.data_ptr(), flat.numel(), out.data_ptr(),
                                  stream)
         ctx.save_for_backward(flat)
-        ctx.lookup = (rows, dim, bloom, padding_idx, sparse, weight.device)
-        return out.view(tuple(ids.shape) + (dim,))
+        ctx.lookup = (rows, dim, bloom, padding_idx, sparse, device, home)
+        return out.view(tuple(ids.shape) + (dim,)).to(home)
 
     @staticmethod
     def backward(ctx, grad_out):
         (flat,) = ctx.saved_tensors
-        rows, dim, bloom, padding_idx, sparse, device = ctx.lookup
+        rows, dim, bloom, padding_idx, sparse, device, home = ctx.lookup
         host = _hooks()
         engine = host._engine_for(device)
         stream = host._stream_for(device)
-        g = grad_out.reshape(flat.numel(), dim).to(torch.float32).contiguous()
+        g = grad_out.reshape(flat.numel(), dim).to(device=device, dtype=torch.float32).contiguous()
         n_rows = engine.embedding_backward_plan(rows, dim, bloom, padding_idx, flat.data_ptr(), flat.numel(),
                                                 count_rows=sparse, stream=stream)
         if sparse:
             idx = torch.empty((1, n_rows), dtype=torch.int64, device=device)
             val = torch.empty((n_rows, dim), dtype=torch.float32, device=device)
             engine.embedding_backward_fill(g.data_ptr(), None, idx.data_ptr(), val.data_ptr(), stream=stream)
-            grad = torch.sparse_coo_tensor(idx, val, (rows, dim), is_coalesced=True)
+            grad = torch.sparse_coo_tensor(idx.to(home), val.to(home), (rows, dim), is_coalesced=True)
         else:
             grad = torch.empty((rows, dim), dtype=torch.float32, device=device)
             engine.embedding_backward_fill(g.data_ptr(), grad.data_ptr(), stream=stream)
-        return grad, None, None, None, None
+            grad = grad.to(home)
+        return grad, None, None, None, None, None
 
 
 def lookup(weight, ids, bloom=None, padding_idx=None, sparse=False):
@@ -67,9 +73,7 @@ def lookup(weight, ids, bloom=None, padding_idx=None, sparse=False):
     A layer that still lives in host memory (the reference's layers are plain torch modules and its tests call them right
     after construction, tests/test_layers.py) is staged onto the HIP device for the call and the result is handed back on
     the table's own device: the gather / hashed-row sum still runs in the gfx950 kernel (there is no CPU compute path;
-    without a HIP device this raises), and gradients flow back to the host table through autograd's copy nodes."""
+    without a HIP device this raises), and the gradient, dense or sparse, comes back on the host as well."""
     home = weight.device
     dev = _hooks()._model_device() if home.type == 'cpu' else home
-    if dev != home:
-        return _Lookup.apply(weight.to(dev), ids.to(dev), bloom, padding_idx, bool(sparse)).to(home)
-    return _Lookup.apply(weight, ids, bloom, padding_idx, bool(sparse))
+    return _Lookup.apply(weight, ids, bloom, padding_idx, bool(sparse), dev)
