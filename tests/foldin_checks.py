@@ -21,6 +21,13 @@ ITEMS = (7, 333)           # 7: a history is full of duplicates and negatives eq
 USERS = (1, 5, 70)
 ROUTES = (0, 1, 1 << 40, 20)   # "foldin_wg_min_len": default, all-workgroup, all-wave, and a crossover inside every mix of lengths
 NN = 3                     # negatives per interaction under adaptive hinge
+# adaptive hinge (and, in warp_checks, warp) at wide n: the gather takes a position's candidates SLK_FOLDIN_NEG_BATCH = 4 at a
+# time -- n = 7 is one full batch and a ragged one, n = 64 sixteen.  Short histories (both routes under "foldin_wg_min_len" = 20,
+# an empty one, a single interaction): the closed loop's cost, and under warp the number of hinge arguments its guard has to keep
+# away from 0, grow with n * m.  (D, n, optimizer): every row layout, every n
+WIDE_NS = (7, 64)
+WIDE_LENGTHS = (37, 0, 3, 1, 9)
+WIDE = [(6, 7, 'adagrad'), (24, 64, 'sgd'), (72, 7, 'sparse_adam'), (64, 64, 'adam_dense')]
 SENTINEL = np.float32(-7.25)
 
 
@@ -61,10 +68,10 @@ def history_lengths(D, H):
 class Problem(object):
     """Histories (CSR), negatives [T][nn][n], frozen item tables and initial rows for H new users."""
 
-    def __init__(self, D, I, H, loss, T, seed=0, lengths=None):
+    def __init__(self, D, I, H, loss, T, seed=0, lengths=None, nn=NN):
         rs = np.random.RandomState(1000 + 7 * D + 3 * I + H + seed)
         self.D, self.I, self.H, self.loss, self.T = D, I, H, loss, T
-        self.nn = NN if loss == 'adaptive_hinge' else 1
+        self.nn = nn if loss == 'adaptive_hinge' else 1
         lens = np.asarray(history_lengths(D, H) if lengths is None else lengths, dtype=np.int64)
         self.off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         self.n = int(self.off[-1])
@@ -117,8 +124,8 @@ class Fold(object):
         neg = pr.neg[t0:t0 + n_steps]
         d_neg = be.alloc(neg if neg.size else np.zeros(1, np.int64))
         d_loss = be.alloc(np.full((n_steps, pr.H), np.nan, dtype=np.float32)) if want_loss else None
-        be.engine.bilinear_foldin(self.tables, self.optim, be.ptr(self.d_off), be.ptr(self.d_items), pr.H, pr.n, pr.loss, NN,
-                                  n_steps, be.ptr(d_neg), be.ptr(d_loss), be.stream)
+        be.engine.bilinear_foldin(self.tables, self.optim, be.ptr(self.d_off), be.ptr(self.d_items), pr.H, pr.n, pr.loss,
+                                  pr.nn if pr.loss == 'adaptive_hinge' else NN, n_steps, be.ptr(d_neg), be.ptr(d_loss), be.stream)
         self.assert_frozen()
         return be.get(d_loss).copy() if want_loss else None
 
@@ -208,6 +215,14 @@ def closed_loop_one_route(be, pr, opt, route, steps):
 
 def check_closed_loop(be, loss, opt, D, I, H, steps=2):
     pr = Problem(D, I, H, loss, steps)
+    for route in ROUTES:
+        closed_loop_one_route(be, pr, opt, route, steps)
+
+
+def check_wide_adaptive(be, D, n, opt, I=ITEMS[1], steps=2):
+    """Adaptive hinge over n candidates per position (WIDE), every route, against the oracle's one-user step."""
+    pr = Problem(D, I, len(WIDE_LENGTHS), 'adaptive_hinge', steps, lengths=WIDE_LENGTHS, nn=n)
+    assert pr.neg.shape == (steps, n, sum(WIDE_LENGTHS))
     for route in ROUTES:
         closed_loop_one_route(be, pr, opt, route, steps)
 

@@ -67,6 +67,10 @@ SCAN_SHAPES = [(64, 1), (64, 15), (64, 16), (64, 17), (64, 255), (64, 256), (64,
                (6, 33), (6, 256), (3, 65)]                                                # vec 1: g 8, g 4
 SCAN_LOSSES = (('bpr', 1), ('adaptive_hinge', 5))
 PAD_SHAPES = [(64, 17), (6, 33)]
+# adaptive hinge at wide n: the pass indexes its dL/dscore as gsn[(b * L + t) * NP + pair], and everything above stops at NP = 6.
+# (D, L) is the grid-stride case's, the smallest shape here that has a running mean (at L = 1 every representation is zero)
+WIDE_NS = (7, 64, 200)
+WIDE_SHAPE = (8, 3)
 
 
 def pick_layout(D):
@@ -509,6 +513,17 @@ def check_isolating(be, D, L, loss, n_neg=1, B=None):
         cand = case.negs.reshape(n_neg, case.B, case.L)
         idle = cand[cand != x.nid[None]]
         assert (rows[idle] == 0).all() and (bias[idle] == 0).all()
+
+
+def check_wide_adaptive(be, n_neg):
+    """Adaptive hinge over n_neg candidates per timestep (WIDE_NS) at WIDE_SHAPE, both forms of the pass: every timestep's chosen
+    candidate, its row and bias against float64; the n_neg - 1 others exactly zero.  The chosen rows are spread over the
+    candidates -- from n = 64 not all among the first six, where the other cases end."""
+    D, L = WIDE_SHAPE
+    case = isolating_case(D, L, 'adaptive_hinge', n_neg)
+    real = case.seqs != 0
+    assert len(np.unique(case.exact.chosen[real])) >= min(real.sum(), n_neg) // 2 and case.exact.chosen[real].max() >= min(6, n_neg // 2)
+    check_isolating(be, D, L, 'adaptive_hinge', n_neg)
 
 
 def check_shared(be, loss, n_neg=1, L=64):

@@ -33,8 +33,9 @@ LAUNCH = dict(epoch_kernel=0)
 SEED = 5
 
 # (kind, D, n, I) of the closed loop, rotated as warp_checks.CLOSED rotates them: adagrad every (D, n) at I = 333; the other kinds
-# every D once with n rotating; every kind the 7-item catalogue at n = 5, D rotating; one case whose NP = 131 lies beyond two
-# wavefronts and crosses every lane-group width of k_softmax_loss
+# every D once with n rotating; every kind the 7-item catalogue at n = 5, D rotating; one case at n = 130: NP = 131 takes
+# k_softmax_loss<64> alone, in its strided form (two full trips of the wavefront and three pairs of a third).  NS takes G = 2, 4, 8;
+# G = 16, 32, 64 with one pair per lane, NP a multiple of 64 and the cap are in tests/wide_negatives_checks.py
 CLOSED = [('adagrad', D, n, 333) for D in DS for n in NS] + \
          [(k, D, NS[(i + j) % 3], 333) for j, k in enumerate(KINDS[1:]) for i, D in enumerate(DS)] + \
          [(k, DS[j % 4], 5, 7) for j, k in enumerate(KINDS)] + [('adagrad', 24, 130, 333)]

@@ -22,6 +22,11 @@ def rotated(i):
 PAIRS = [(loss, opt) for loss in fc.LOSSES for opt in fc.KINDS]
 
 
+@pytest.mark.parametrize('D,n,opt', fc.WIDE)
+def test_adaptive_hinge_over_many_candidates_against_the_oracle(be, D, n, opt):
+    fc.check_wide_adaptive(be, D, n, opt)
+
+
 @pytest.mark.parametrize('i', range(len(PAIRS)))
 def test_closed_loop_against_the_oracle(be, i):
     loss, opt = PAIRS[i]

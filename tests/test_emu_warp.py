@@ -93,6 +93,17 @@ def test_fold_in_closed_loop(be, opt):
         wk.check_fold_closed_loop(be, opt, D, I, H, n)
 
 
+@pytest.mark.parametrize('D,n,opt', wk.FOLD_WIDE)
+def test_the_wide_fold_in_seeds_keep_the_restatement_away_from_ties(D, n, opt):
+    for o in ('sgd', opt):
+        wk.check_fold_seed_meets_the_guard(D, 333, 5, n, opt=o, pr=wk.wide_problem(D, n))
+
+
+@pytest.mark.parametrize('D,n,opt', wk.FOLD_WIDE)
+def test_fold_in_closed_loop_over_many_candidates(be, D, n, opt):
+    wk.check_fold_closed_loop(be, opt, D, 333, 5, n, pr=wk.wide_problem(D, n))
+
+
 @pytest.mark.parametrize('D', wk.DS)
 def test_fold_in_batch_and_step_composition(be, D):
     for I, n in ((333, 3), (7, 5)):

@@ -18,6 +18,11 @@ def be():
 PAIRS = [(loss, opt) for loss in fc.LOSSES for opt in fc.KINDS]
 
 
+@pytest.mark.parametrize('D,n,opt', fc.WIDE)
+def test_adaptive_hinge_over_many_candidates_against_the_oracle(be, D, n, opt):
+    fc.check_wide_adaptive(be, D, n, opt)
+
+
 @pytest.mark.parametrize('D', fc.DS)
 @pytest.mark.parametrize('i', range(len(PAIRS)))
 def test_closed_loop_against_the_oracle(be, i, D):

@@ -33,6 +33,11 @@ def test_losses_one_term_per_row(be, loss, n_neg):
     sx.check_isolating(be, 64, 17, loss, n_neg)
 
 
+@pytest.mark.parametrize('n_neg', sx.WIDE_NS)
+def test_adaptive_hinge_over_many_candidates(be, n_neg):
+    sx.check_wide_adaptive(be, n_neg)
+
+
 @pytest.mark.parametrize('loss', sx.LOSSES)
 def test_losses_long_runs(be, loss):
     sx.check_shared(be, loss, 5, L=17)

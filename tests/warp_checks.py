@@ -53,6 +53,11 @@ SEEDS = {}
 FOLD_CLOSED = [(6, 333, 5, 1), (24, 333, 70, 3), (64, 333, 5, 5), (72, 333, 5, 3)]
 FOLD_CLOSED_7 = [(D, 7, 5, 5) for D in DS]
 FOLD_SEEDS = {}
+# fold-in at wide n, (D, n, optimizer): foldin_checks.WIDE's shapes over foldin_checks.WIDE_LENGTHS (59 positions, n * 59 hinge
+# arguments per step for the guard to hold off 0 -- the histories of FOLD_CLOSED, with 300 interactions in one of them, would
+# leave no seed at n = 64)
+FOLD_WIDE = fc.WIDE
+FOLD_WIDE_SEEDS = {}
 
 
 def hyper(kind):
@@ -495,16 +500,20 @@ def fold_closed_loop(be, pr, opt, route, steps):
                     assert not (d > tol).any(), (what, tab, nm, float(d.max()), float(tol.min()))
 
 
-def check_fold_closed_loop(be, opt, D, I, H, n, steps=2):
-    pr = Problem(D, I, H, steps, n=n, seed=FOLD_SEEDS.get((D, I, H, n), 0))
+def wide_problem(D, n, steps=2, I=333):
+    return Problem(D, I, len(fc.WIDE_LENGTHS), steps, n=n, seed=FOLD_WIDE_SEEDS.get((D, n), 0), lengths=fc.WIDE_LENGTHS)
+
+
+def check_fold_closed_loop(be, opt, D, I, H, n, steps=2, pr=None):
+    pr = pr or Problem(D, I, H, steps, n=n, seed=FOLD_SEEDS.get((D, I, H, n), 0))
     for route in fc.ROUTES:
         fold_closed_loop(be, pr, opt, route, steps)
 
 
-def check_fold_seed_meets_the_guard(D, I, H, n, steps=2, opt='sgd'):
+def check_fold_seed_meets_the_guard(D, I, H, n, steps=2, opt='sgd', pr=None):
     """No engine: every user's hinge arguments over the steps of the float64 restatement alone, 2 * GUARD away from 0 (SGD's
     trajectory; the closed loop asserts GUARD on every step of every optimizer's own)."""
-    pr = Problem(D, I, H, steps, n=n, seed=FOLD_SEEDS.get((D, I, H, n), 0))
+    pr = pr or Problem(D, I, H, steps, n=n, seed=FOLD_SEEDS.get((D, I, H, n), 0))
     z = lambda x: np.zeros(np.shape(x), np.float32)
     pre = [pr.U.copy(), pr.b.copy(), z(pr.U), z(pr.b), z(pr.U), z(pr.b)]
     for t in range(steps):
