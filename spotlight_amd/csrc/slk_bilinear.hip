@@ -98,6 +98,7 @@ __global__ __launch_bounds__(256) void k_user_pass(slk_pass_args a) {
     // t + 2 in front of turn t's own row loads.  (Only the user's owner -- this group, in turn t + 1 -- writes that flag byte.)
     // SLK_PP_PIPE >= 2: the turn's (positive, negative) item pair travels with its key, so that a head issues its user row, both
     // item rows and the biases in ONE round trip; >= 3: and the row's optimizer state with them (as the latency-bound form does).
+    // (Two further steps were measured and not kept: DESIGN.md section 6 "Round 8", profiles/r08_a_pass_waits.md.)
     constexpr bool PIPE = PP && !LAT && !ULONG && SLK_PP_PIPE >= 1;
     constexpr bool PIPE_IDS = PIPE && SLK_PP_PIPE >= 2;
     uint32_t pk_key = 0u, pk_prev = 0u, pk_flag = 0u, pn_key = 0u, pn_prev = 0u;

@@ -323,17 +323,24 @@ __device__ __forceinline__ void slk_explicit_loss_weighted(int loss_kind, float 
 // ---------------------------------------------------------------------------------------
 // ITEM PASS
 // ---------------------------------------------------------------------------------------
-// One occurrence's contribution, read from its record.
-template <int VEC, int MODE>
-__device__ __forceinline__ void slk_item_contrib(const slk_pass_args &a, uint32_t r, int D, int d0, bool on,
-                                                 slk_vec<VEC> &c, float &gb) {
+// One occurrence's contribution, read from its record -- in three parts, so that a caller with several occurrences in hand
+// (k_item_pass step (2b)) can issue the loads of all of them before it consumes any: a load and its use inside one divergent
+// region compile to load, wait, use, and the next occurrence's load goes out a full round trip later.
+//   slk_item_ref      issues the occurrence's SCALAR load (dL/dscore; ping-pong: the {dL/dscore, src} pair) and returns where its
+//                     row stands.  The address depends on a loaded value only in the ping-pong forms (src).
+//   slk_item_row      issues the row load.
+//   slk_item_combine  the contribution from the two, once they have arrived.
+// `own` (SEQ): the occurrence is the sequence's own item, whose row is taken as it is.
+template <int MODE>
+__device__ __forceinline__ const float *slk_item_ref(const slk_pass_args &a, uint32_t r, int D, float &gb, bool &own) {
+    own = false;
     if (MODE == SLK_ITEM_ROW) {
         const float *rec = a.snap + (size_t)(r - a.begin) * a.RS;
         gb = rec[D];
-        c = on ? slk_vload<VEC>(rec + d0) : slk_vzero<VEC>();
+        return rec;
     } else if (MODE == SLK_ITEM_BLK) {
         gb = a.snap[slk_blk_scalar(r, D)];
-        c = on ? slk_vload<VEC>(a.snap + slk_blk_row(r, D) + d0) : slk_vzero<VEC>();
+        return a.snap + slk_blk_row(r, D);
     } else {
         const uint32_t NP = (uint32_t)a.NP;
         const uint32_t pos = (NP == 2) ? (r >> 1) : (r / NP);
@@ -344,40 +351,69 @@ __device__ __forceinline__ void slk_item_contrib(const slk_pass_args &a, uint32_
             // left untouched (no record was written)
             const uint2 t = reinterpret_cast<const uint2 *>(a.gsn)[r - a.begin * 2u];
             memcpy(&gb, &t.x, 4);
-            const float *urow = ((t.y >> 31) ? a.P0alt : a.P[0]) + (size_t)(t.y & 0x7fffffffu) * D;
-            const slk_vec<VEC> u = on ? slk_vload_if_nt<VEC>(urow + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) c.v[i] = gb * u.v[i];
+            return ((t.y >> 31) ? a.P0alt : a.P[0]) + (size_t)(t.y & 0x7fffffffu) * D;
         } else if (MODE == SLK_ITEM_SNAP || MODE == SLK_ITEM_SNAPALL) {
             gb = a.gsn[r - a.begin * NP];
-            // several negatives per interaction (adaptive hinge): only the positive and the selected
-            // negative carry a gradient, so the row is fetched only when dL/dscore != 0 (a dependent
-            // load; with one negative every occurrence is live and both loads are issued at once).
-            // SLK_ITEM_SNAPALL (sampled softmax): every occurrence is live, so the row is fetched without looking at dL/dscore
-            // and the tile's gathers are all in flight together (a compile-time form: as a run-time flag in this condition the
-            // loads stayed behind the branch and gained nothing, DESIGN.md 4b "Sampled softmax").  An occurrence whose dL/dscore
-            // underflowed to exactly 0 then adds 0 * u where the skipped load adds a zero vector: the same for every finite row.
-            const slk_vec<VEC> u = (on && (MODE == SLK_ITEM_SNAPALL || NP <= 2 || gb != 0.0f)) ? slk_vload_if_nt<VEC>(rec + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) c.v[i] = gb * u.v[i];
+            return rec;
         } else {
             // PoolNet (slk_seq.hip): record = [representation | the own item's ready-made contribution g * representation +
             // history gradient].  The own item (s == 0) takes the second half as it is, a sampled item g times the first:
             // ONE 4D-byte read per occurrence (rounds 1-4: both halves for s == 0)
             gb = a.gsn[r - a.begin * NP];
-            const slk_vec<VEC> u = on ? slk_vload<VEC>(rec + (s == 0 ? D : 0) + d0) : slk_vzero<VEC>();
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) c.v[i] = s == 0 ? u.v[i] : gb * u.v[i];
+            own = s == 0;
+            return rec + (own ? D : 0);
         }
     }
+}
+
+// Whether the row has to be looked at only once dL/dscore is known.  Several negatives per interaction (adaptive hinge): only
+// the positive and the selected negative carry a gradient, so the row is fetched only when dL/dscore != 0 -- a dependent
+// load.  With one negative every occurrence is live and the row load does not wait for the scalar.
+// SLK_ITEM_SNAPALL (sampled softmax): every occurrence is live, so the row is fetched without looking at dL/dscore (a
+// compile-time form: as a run-time flag in the condition the loads stayed behind the branch and gained nothing, DESIGN.md 4b
+// "Sampled softmax").  An occurrence whose dL/dscore underflowed to exactly 0 then adds 0 * u where the skipped load adds a
+// zero vector: the same for every finite row.
+template <int MODE>
+__device__ __forceinline__ bool slk_item_row_skips(const slk_pass_args &a) {
+    return MODE == SLK_ITEM_SNAP && a.NP > 2;
+}
+
+template <int VEC, int MODE>
+__device__ __forceinline__ slk_vec<VEC> slk_item_row(const slk_pass_args &a, const float *row, int d0) {
+    if (SLK_ITEM_IS_SNAP(MODE)) return slk_vload_if_nt<VEC>(row + d0, (SLK_NT_OF(a) & 32) != 0);
+    return slk_vload<VEC>(row + d0);
+}
+
+template <int VEC, int MODE>
+__device__ __forceinline__ void slk_item_combine(float gb, bool own, const slk_vec<VEC> &u, slk_vec<VEC> &c) {
+    if (MODE == SLK_ITEM_ROW || MODE == SLK_ITEM_BLK) {
+        c = u;
+    } else if (MODE == SLK_ITEM_SEQ) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) c.v[i] = own ? u.v[i] : gb * u.v[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) c.v[i] = gb * u.v[i];
+    }
+}
+
+// The three parts one after the other: an occurrence on its own (the spill walk of k_item_pass).
+template <int VEC, int MODE>
+__device__ __forceinline__ void slk_item_contrib(const slk_pass_args &a, uint32_t r, int D, int d0, bool on,
+                                                 slk_vec<VEC> &c, float &gb) {
+    bool own;
+    const float *row = slk_item_ref<MODE>(a, r, D, gb, own);
+    const slk_vec<VEC> u = (on && (!slk_item_row_skips<MODE>(a) || gb != 0.0f)) ? slk_item_row<VEC, MODE>(a, row, d0) : slk_vzero<VEC>();
+    slk_item_combine<VEC, MODE>(gb, own, u, c);
 }
 
 // A block walks tiles of T = 4 * (256/G) consecutive positions of the item-sorted occurrence
 // list.  Per tile: (1) keys + payloads -> LDS; wave 0 compacts the heads of the runs of equal keys
 // that START in the tile into a list (plus position 0 when it continues the previous tile's last run), head r belongs
 // to row group r mod GPB (an even 1-2 heads per group); (2) a group issues the loads of its first head's item row +
-// optimizer state TOGETHER with its four record gathers (every load independent: one HBM round trip covers both) and
-// parks the contributions in LDS; (3) each run is summed from LDS by its owner group (a run that spills into the next
+// optimizer state TOGETHER with its four record gathers (every load independent: one HBM round trip covers both -- the
+// gathers are issued in a loop of their own and multiplied behind it, see step (2b); until round 8 the source said so and
+// the compiled kernel made one round trip per gather) and parks the contributions in LDS; (3) each run is summed from LDS by its owner group (a run that spills into the next
 // tile is finished from global memory; rows of a run that started in the previous tile are skipped -- its owner already
 // took them) and the optimizer is applied to that item's row and bias.
 // LONG runs -- a run that wholly covers at least one tile: a popular item of a skewed dataset, a hashed row of a small
@@ -397,7 +433,9 @@ __device__ __forceinline__ void slk_item_contrib(const slk_pass_args &a, uint32_
 // hashed rows) while the bias table is indexed by the item id itself.
 enum { SLK_PART_BOTH = 0, SLK_PART_ROWS = 1, SLK_PART_BIAS = 2 };
 #ifndef SLK_ITEM_WAVES
-#define SLK_ITEM_WAVES 7  // occupancy target of the item pass (waves per SIMD): 72 VGPRs, no spills with NPRE 1
+#define SLK_ITEM_WAVES 7  // occupancy target of the item pass (waves per SIMD): a budget of 72 VGPRs.  The D = 64 Adagrad instances
+                          // of C2 fit it without scratch (ping-pong form 69, one-table form 72); narrower row groups and the LONG
+                          // forms spill 8-24 bytes per lane (profiles/r08_a_pass_waits.md)
 #endif
 #ifndef SLK_ITEM_NPRE
 #define SLK_ITEM_NPRE 1  // heads per group whose row + state loads ride along with the record gather; measured
@@ -592,14 +630,13 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(NPRE_ > SLK_ITEM_NPRE ? 4 : S
                     f = (((j == 0 && (first_tile || inherits_long)) || key != s_key[j]) && item != a.pad_item &&
                          item != a.pad_item2 && (!SKIP1 || s_multi[j])) ? 1 : 0;  // (a once-only item is not a head: nothing to do)
                 }
-                int incl = f;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int up = __shfl_up(incl, d, 64);
-                    if ((int)threadIdx.x >= d) incl += up;
-                }
+                // the flags are one bit each: a head's rank is a population count of the wave's ballot (a six-step shuffle scan
+                // before: six dependent LDS permutes on the path every wave of the workgroup waits for, and six lane offsets
+                // that the compiler kept in registers across the gathers)
+                const unsigned long long fm = __ballot(f);
+                const int incl = __popcll(fm & (~0ull >> (63 - (int)threadIdx.x)));
                 if (f) s_head[base + incl - 1] = (uint16_t)j;
-                base += __shfl(incl, 63, 64);
+                base += __popcll(fm);
             }
             if (threadIdx.x == 0) s_nheads = base;
         }
@@ -642,33 +679,62 @@ __global__ __launch_bounds__(256) SLK_WAVES_PER_EU(NPRE_ > SLK_ITEM_NPRE ? 4 : S
         }
 
         // (2b) gather: position j = grp + it * GPB
-        slk_vec<VEC> c[4];
+        // ISSUE, THEN CONSUME.  The four positions' loads are issued in loops of their own and the products are formed behind
+        // them, outside every divergent region: with the load and its use in one `if (mine)` body the compiler waits for each
+        // row before it computes the next position's address -- four dependent round trips per tile (eight in the forms that
+        // read dL/dscore themselves) where one (two) suffices.  A position that is not the group's has g = 0 and a zero row,
+        // and 0 * 0 is the +0 it had before.
+        //   GSPF:       g from LDS, the four user rows in ONE trip
+        //   ROW, BLK:   the four scalars and the four rows in ONE trip (the addresses come from the payload alone)
+        //   the rest:   the four scalars in one trip, the four rows in the next -- all of them where every occurrence is
+        //               live; several negatives (slk_item_row_skips): a row is fetched only behind its dL/dscore != 0
+        slk_vec<VEC> c[4], u[4];
         float g[4];
+        const float *urow[4];
+        bool mine[4], own[4];
+        constexpr bool ONE_TRIP = GSPF || MODE == SLK_ITEM_ROW || MODE == SLK_ITEM_BLK;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int j = grp + it * GPB;
             g[it] = 0.0f;
-            c[it] = slk_vzero<VEC>();
+            u[it] = slk_vzero<VEC>();
+            urow[it] = nullptr;
+            own[it] = false;
             // rows of a SHORT run inherited from the previous tile belong to that tile's owner
-            bool mine = j < tn && (!inherits || inherits_long || s_key[j + 1] != s_key[0]);
-            if (mine) {
+            mine[it] = j < tn && (!inherits || inherits_long || s_key[j + 1] != s_key[0]);
+            if (mine[it]) {
                 // never-updated keys (padding_idx rows, the dead entries of a live list) have no
                 // record worth reading -- a dead entry's payload is not even a valid reference
                 const uint32_t item = s_key[j + 1] & a.imask;
-                mine = item != a.pad_item && item != a.pad_item2 && (!SKIP1 || s_multi[j]);
+                mine[it] = item != a.pad_item && item != a.pad_item2 && (!SKIP1 || s_multi[j]);
             }
-            if (mine && GSPF) {
+            if (mine[it] && GSPF) {
                 g[it] = s_g[j];
                 const uint32_t src = s_src[j];
-                const float *urow = ((src >> 31) ? a.P0alt : a.P[0]) + (size_t)(src & 0x7fffffffu) * D;
-                const slk_vec<VEC> u = rows_on ? slk_vload_if_nt<VEC>(urow + d0, (SLK_NT_OF(a) & 32) != 0) : slk_vzero<VEC>();
+                urow[it] = ((src >> 31) ? a.P0alt : a.P[0]) + (size_t)(src & 0x7fffffffu) * D;
+            } else if (mine[it]) {
+                urow[it] = slk_item_ref<MODE>(a, s_pay[j], D, g[it], own[it]);
+            }
+            if (ONE_TRIP && mine[it] && rows_on) u[it] = slk_item_row<VEC, MODE>(a, urow[it], d0);
+        }
+        if (!ONE_TRIP) {
+            if (slk_item_row_skips<MODE>(a)) {
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) c[it].v[i] = g[it] * u.v[i];
-            } else if (mine) {
-                slk_item_contrib<VEC, MODE>(a, s_pay[j], D, d0, rows_on, c[it], g[it]);
+                for (int it = 0; it < 4; ++it)
+                    if (mine[it] && rows_on && g[it] != 0.0f) u[it] = slk_item_row<VEC, MODE>(a, urow[it], d0);
+            } else {
+#pragma unroll
+                for (int it = 0; it < 4; ++it)
+                    if (mine[it] && rows_on) u[it] = slk_item_row<VEC, MODE>(a, urow[it], d0);
             }
         }
-        if (KEYPF && tile + gridDim.x < ntiles) tile_fetch(tile + gridDim.x);  // in flight behind the gathers
+        // The next tile's keys + payloads, behind the gathers.  In flight WITH them in the compiled ping-pong (GSPF) forms only: in
+        // the forms that make two trips the compiler waits for the rows first and gives each of these loads a wait of its own
+        // (the parent's one-table form had the rows consumed by then as well and overlapped the two loads with each other):
+        // profiles/r08_a_pass_waits.md
+        if (KEYPF && tile + gridDim.x < ntiles) tile_fetch(tile + gridDim.x);
+#pragma unroll
+        for (int it = 0; it < 4; ++it) slk_item_combine<VEC, MODE>(g[it], own[it], u[it], c[it]);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int j = grp + it * GPB;
